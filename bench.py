@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s on the RTIOW final scene (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, the timed launches' kernel time); --dump-outputs DIR also writes
+the image of the last timed step to DIR/image.npy (float32; the same inputs,
+so the same file, in every run with the same arguments).  Everything else
+described below — the executed-work count behind roofline.achieved, the
+committed PMC records, the one-shot and brute-force launches, the gather
+check, the CPU baselines — runs only with --full.
 
 One step = one full render of the config-2 workload: the final random-spheres
 scene (487 spheres, glibc seed 1 as the reference), 1200x800, 500 spp, depth
@@ -320,6 +328,24 @@ def busy_ms_per_launch(events):
         else:
             cur_e = max(cur_e, b)
     return (total + cur_e - cur_s) / len(events)
+
+
+DUMP_MAX_BYTES = 60 << 20  # a dump stays under 64e6 bytes, .npy header included
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the image the last timed step produced (what a caller of
+    the timed path receives: this rank's rows at N = 1, the un-permuted frame
+    on rank 0 at N > 1) -> path/image.npy, float32.  An image above 60 MiB
+    (config 5) is written as a fixed sample of its rows (default_rng(0), in
+    ascending order), the same rows in every run."""
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    row_bytes = image[0].nbytes
+    if image.nbytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(image.shape[0], DUMP_MAX_BYTES // row_bytes, replace=False))
+        image = image[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), image)
 
 
 class StubEvent:
@@ -649,9 +675,17 @@ def main():
                          "profiles/r06/rccl_one_rank/ab_pipeline3.txt)")
     ap.add_argument("--strip-of", type=int, default=0,
                     help="analysis only: time ONE rank's interleaved strip of an N-GPU run on this GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the executed-work count (roofline.achieved), "
+                         "the committed PMC records, the one-shot and brute-force launches, the gather check and "
+                         "the CPU baselines (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's image to DIR/image.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_exec_counts = args.timed_only = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(args, sys.argv[1:]))
     ws = int(os.environ.get("WORLD_SIZE", "1"))
@@ -821,6 +855,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll)
         collective("all_reduce(max) of the timed region", dist.all_reduce, t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # before any side launch renders into these buffers again
+        if DIST:
+            dump_outputs(args.dump_outputs, rdist.unpermute([g.cpu().numpy() for g in gathered], H))
+        else:
+            dump_outputs(args.dump_outputs, strips[(nstep[0] - 1) % len(strips)].cpu().numpy())
 
     # GPU time per launch: the union of the launches' intervals / K (launches on
     # two streams overlap at their ends); launch_ms = the mean of each launch's
@@ -950,7 +989,7 @@ def main():
         if args.accel == "none":
             flop_exec = flop_eq  # brute force executes every miss test
         elif args.no_exec_counts or STUB:
-            flop_exec, why = None, "skipped (stub renderer)" if STUB else "skipped (--no-exec-counts)"
+            flop_exec, why = None, "skipped (stub renderer)" if STUB else "skipped (needs --full without --no-exec-counts)"
         else:
             counts, why = executed_counts(W, H, SPP, row0, row_step, nrows, args.accel, args.kernel)
             flop_exec = executed_flop(counts, args.accel) if counts else None
@@ -963,7 +1002,8 @@ def main():
         lib_path = None if STUB else rt._abi.LIB_PATH
         ksym = None if STUB else timed_kernel_symbol(timed_sched, r.grid_info()[0][1] == 1)
         pmc = os.path.join(REPO, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc) and args.workload == "config2" and not args.strip_of and N == 1 and not STUB:  # measured on config 2
+        quote_pmc = args.full and args.workload == "config2" and not args.strip_of and N == 1 and not STUB  # measured on config 2
+        if os.path.exists(pmc) and quote_pmc:
             try:
                 rec, pmc_notes["traffic"] = pmc_guard(json.load(open(pmc)).get(args.accel), lib_path, ksym)
                 traffic = rec["hbm_bytes_per_launch"] if rec else None
@@ -1020,8 +1060,7 @@ def main():
         # included) and how busy the VALU issue is — the bound of this
         # divergent kernel
         pmcv = os.path.join(REPO, "profiles", "pmc_valu.json")
-        if (os.path.exists(pmcv) and args.workload == "config2" and args.accel == "grid" and not args.strip_of and N == 1
-                and not STUB):
+        if os.path.exists(pmcv) and quote_pmc and args.accel == "grid":
             try:
                 pv, pmc_notes["pmc"] = pmc_guard(json.load(open(pmcv)), lib_path, ksym)
                 roof["pmc"] = None
@@ -1182,8 +1221,10 @@ def bench_nw(args):
     stream = torch.cuda.Stream(dev)
     torch.cuda.set_stream(stream)
     ev = []
+    gathered = None
 
     def step(record):
+        nonlocal gathered
         if record:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
@@ -1192,8 +1233,8 @@ def bench_nw(args):
             e1.record(stream)
             ev.append((e0, e1))
         if DIST:
-            collective("gather of the strips", rdist.gather_strips, strip if coll.type == "cuda" else strip.cpu(), rank, N,
-                       dst=0)
+            gathered = collective("gather of the strips", rdist.gather_strips,
+                                  strip if coll.type == "cuda" else strip.cpu(), rank, N, dst=0)
 
     for _ in range(args.warmup):
         step(False)
@@ -1213,6 +1254,9 @@ def bench_nw(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll)
         collective("all_reduce(max) of the timed region", dist.all_reduce, t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     rdist.unpermute([g.cpu().numpy() for g in gathered], Hn) if DIST else strip.cpu().numpy())
     # GPU time per launch: the union of the launches' intervals / K (launches on
     # two streams overlap at their ends); launch_ms = the mean of each launch's
     # own start-to-end time, which counts the overlap once per launch
@@ -1228,7 +1272,7 @@ def bench_nw(args):
         if counts and counts["segments"] != segs:
             why, counts = f"stats build segments {counts['segments']} != product {segs}", None
     elif args.no_exec_counts:
-        why = "skipped (--no-exec-counts)"
+        why = "skipped (needs --full without --no-exec-counts)"
     achieved = counts["flop"] / (kernel_ms * 1e-3) / 1e12 if counts else None
     if rank == 0:
         samples = Wn * Hn * spp

@@ -27,7 +27,7 @@ def test_bench_n_ranks_line_schema(n, pipeline, tmp_path):
     steps = 7
     pa = ["--pipeline", str(pipeline)] if pipeline else []
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", "1",
-                        *pa], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+                        "--full", *pa], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     pipeline = pipeline or 3
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
@@ -102,7 +102,7 @@ def test_forced_one_rank_runs_the_n_rank_path(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RTMI_DIST_BACKEND="gloo", RTMI_BENCH_STUB="1", OMP_NUM_THREADS="1", RTMI_DIST_FORCE="1")
-    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1"], bench.free_port())
+    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"], bench.free_port())
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
@@ -127,6 +127,37 @@ def test_force_without_launcher_is_the_plain_path(tmp_path):
     assert "dist" not in d and "dist_rehearsal" not in d["config"] and d["config"]["partition"] == "single GPU"
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_plain_run_is_lean_and_dumps_the_last_steps_image(n, tmp_path):
+    """Without --full the line keeps the headline fields and none of the side
+    legs (one-shot, gather check, CPU baseline); --dump-outputs DIR writes the
+    image of the last timed step, un-permuted on rank 0 at N > 1 (800 rows
+    ragged over 3 ranks), as DIR/image.npy in float32: here the stub's pixel
+    (i, j) channel c = (j * W + i) * 3 + c."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(RTMI_DIST_BACKEND="gloo", RTMI_BENCH_STUB="1", OMP_NUM_THREADS="1")
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env,
+                       cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == n and d["steps"] == 4 and d["unit"] == "Msamples/s" and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] - 1200 * 800 * 500 / (d["ms_per_step"] * 1e-3) / 1e6) <= 2e-3 * d["value"]
+    assert d["one_shot"] is None and d["one_shot_msamples_per_s"] is None
+    assert "gather_check" not in d and "cpu_baseline" not in d
+    assert ("dist" in d) == (n > 1)
+    assert os.listdir(out) == ["image.npy"]
+    img = np.load(out / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (800, 1200, 3)
+    assert np.array_equal(img, np.arange(800 * 1200 * 3, dtype=np.float32).reshape(800, 1200, 3))
+
+
 
 @pytest.mark.parametrize("n,mode", [(2, "side"), (3, "side")])
 def test_side_gathers(n, mode, tmp_path):
@@ -135,7 +166,8 @@ def test_side_gathers(n, mode, tmp_path):
     the line and the gather check are the same."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RTMI_DIST_BACKEND="gloo", RTMI_BENCH_STUB="1", OMP_NUM_THREADS="1", RTMI_BENCH_GATHER=mode)
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(p.stdout.splitlines()[-1])

@@ -109,6 +109,25 @@ def test_busy_ms_per_launch_unions_overlapping_launches():
     assert bench.busy_ms_per_launch(pairs([(5, 6), (0, 2)])) == 1.5  # a gap is not counted; any order
 
 
+def test_dump_outputs_samples_the_same_rows_of_a_large_image(tmp_path, monkeypatch):
+    """--dump-outputs: an image under the size cap is written whole, a larger
+    one (config 5) as the same seeded sample of its rows in every run."""
+    import numpy as np
+
+    img = np.arange(40 * 5 * 3, dtype=np.float32).reshape(40, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), img)
+    assert 1200 * 800 * 12 < bench.DUMP_MAX_BYTES < 3840 * 2160 * 12  # the headline frame whole, config 5 sampled
+    assert bench.DUMP_MAX_BYTES + 128 <= 64_000_000  # with the .npy header
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * img[0].nbytes + 7)
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img + 0.0)
+    got = np.load(tmp_path / "b" / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (10, 5, 3) and np.array_equal(got, np.load(tmp_path / "c" / "image.npy"))
+    rows = (got[:, 0, 0] / 15).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, img[rows])
+
+
 LIB = os.path.join(REPO, "a_dive_into_ray_tracing_amd", "lib", "librtmi.so")
 
 

@@ -1054,6 +1054,34 @@ def test_overlapped_contexts_strips_equal_frame(config2, final_world):
     assert np.array_equal(rdist.unpermute([s.cpu().numpy() for s in strips], H), img)
 
 
+def test_bench_plain_run_dumps_the_timed_image(config2, tmp_path):
+    """A plain `bench.py --steps 3 --warmup 1 --dump-outputs DIR` prints one
+    line with the headline fields and none of the --full legs, and
+    DIR/image.npy is the image its last timed step rendered (step 3 of the
+    steps alternating over two contexts and buffers): the config-2 frame,
+    bit for bit."""
+    import json
+    import subprocess
+    import sys
+
+    _, img = config2
+    p = subprocess.run([sys.executable, os.path.join(O.REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=120,
+                       cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "Msamples/s"
+    assert d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] - 1200 * 800 * 500 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
+    assert d["one_shot"] is None and d["roofline"]["brute_force"] is None and "cpu_baseline" not in d
+    assert d["roofline"]["achieved"] is None and d["roofline"]["kernel_ms"] > 0
+    assert os.listdir(tmp_path / "out") == ["image.npy"]
+    got = np.load(tmp_path / "out" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+
+
 @pytest.mark.parametrize("which", [0, 1], ids=["sqrt", "reciprocal"])
 def test_exact_math_exhaustive(which):
     """The kernels' short correctly rounded sqrt and reciprocal (rtmi_path.h

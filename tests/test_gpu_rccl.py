@@ -25,7 +25,8 @@ def test_n_rank_path_through_rccl_at_one_rank(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                            "RTMI_DIST_BACKEND", "RTMI_BENCH_STUB")}
     env.update(RTMI_DIST_FORCE="1", RTMI_DIST_TIMEOUT_S="120")
-    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "3", "--no-cpu-baseline", "--no-exec-counts"],
+    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "3", "--full", "--no-cpu-baseline",
+                                   "--no-exec-counts"],
                                bench.free_port())
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]

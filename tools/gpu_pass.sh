@@ -18,9 +18,9 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; tail -4 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
   cp gpurun_out/parity_stats.json $OUT/ 2>/dev/null
 fi
-echo "== bench" && timeout -k 10 400 python -u bench.py $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+echo "== bench" && timeout -k 10 400 python -u bench.py --full $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
-echo "== strip 1/8" && timeout -k 10 200 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-exec-counts --strip-of 8 > $OUT/strip8.json 2> $OUT/strip8.err || exit 1
+echo "== strip 1/8" && timeout -k 10 200 python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-exec-counts --strip-of 8 > $OUT/strip8.json 2> $OUT/strip8.err || exit 1
 python -c "import json; d=json.load(open('$OUT/strip8.json')); print('strip8', d['ms_per_step'], d['roofline']['kernel_ms'], d['one_shot'])"
 [ -n "$SKIP_PROF" ] && exit 0
 echo "== rocprof kernel trace"

@@ -12,7 +12,7 @@ OUT=gpurun_out/${TAG:-rccl_one_rank}; mkdir -p $OUT
 run() {  # name, bench args...
   local name=$1; shift
   RTMI_DIST_FORCE=1 NCCL_DEBUG=WARN timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node=1 \
-    --master-addr 127.0.0.1 --master-port ${PORT:-29533} bench.py --gpus 1 --no-cpu-baseline "$@" \
+    --master-addr 127.0.0.1 --master-port ${PORT:-29533} bench.py --full --gpus 1 --no-cpu-baseline "$@" \
     > $OUT/$name.json 2> $OUT/$name.err || { tail -30 $OUT/$name.err; return 1; }
   python - $OUT/$name.json <<'PY'
 import json, sys
