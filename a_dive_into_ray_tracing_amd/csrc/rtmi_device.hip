@@ -285,7 +285,12 @@ constexpr bool acc_gmem(int A) { return A >= 4; }
 // absorption, or the scattered ray with its robustness offset.  Returns true
 // when the path ended: col is then its colour (black when absorbed or out of
 // depth).  Shared by every fast kernel, so they compute identical paths.
-template <int ACC>
+// FIRST: the camera segment of a primary batch (render_kernel's pool refill):
+// T is the constant (1, 1, 1) and the depth the constant 0, neither is read
+// or written (1.0f * x == x, so the sky colour and, for the adopting lane,
+// the attenuation come out the same bits), and `depth` returns the hit
+// instead: 2 x the sphere's scene index + 1 for a dielectric.
+template <int ACC, bool FIRST = false>
 __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const SpherePair *__restrict__ pairs,
                                              const RenderArgs &a, V3<float> &o, V3<float> &d, V3<float> &T,
                                              int &depth, Xoro &rng, V3<float> &col, SegCounters &cnt,
@@ -320,7 +325,8 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
     );
   }
 #if RTMI_TRACE
-  cnt.cyc_hit += __builtin_amdgcn_s_memtime() - cyc0;
+  // (the phase build of a batch kernel keeps its batch-pass clock here)
+  if constexpr (!(RTMI_TRACE_PHASES && acc_grid(ACC))) cnt.cyc_hit += __builtin_amdgcn_s_memtime() - cyc0;
 #endif
 #if RTMI_CHECK
   if (k >= a.n) atomicAdd(&segments[7], 1ull << 32);
@@ -343,7 +349,8 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
   if (kind != RT_MAT_LAMBERTIAN) inv_len = drcp(dsqrt(dot<true>(d, d)));
   if (miss) {
     const V3<float> sk = sky_fast(d, inv_len);
-    col = mk(T.x * sk.x, T.y * sk.y, T.z * sk.z);
+    if constexpr (FIRST) col = sk;
+    else col = mk(T.x * sk.x, T.y * sk.y, T.z * sk.z);
     return true;
   }
   V3<float> p, nrm, at, nd;
@@ -351,7 +358,7 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
   hit_record_fast(geomk, sh0k.x, o, d, t, p, nrm, front);
   if (!scatter_fast(sh0k, sh1k, d, nrm, front, rng, at, nd, inv_len))
     return true;  // absorbed (metal below the surface): black, main.cpp:78
-  T = mk(T.x * at.x, T.y * at.y, T.z * at.z);
+  if constexpr (!FIRST) T = mk(T.x * at.x, T.y * at.y, T.z * at.z);
   // float robustness: start the next segment
   // 2^-14 * (1 + |p|_inf) off the surface, on the side the scattered ray
   // leaves on, so float hit-point error (~1e-6) cannot re-hit the surface
@@ -365,6 +372,10 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
   d = nd;
   // depth exhausted: black, main.cpp:58-60 (the depth is the low 24 bits:
   // render_kernel keeps the path's pixel above them)
+  if constexpr (FIRST) {
+    depth = (kk << 1) | (kind == RT_MAT_DIELECTRIC ? 1 : 0);
+    return 1 >= a.max_depth;
+  }
   return (++depth & 0xFFFFFF) >= a.max_depth;
 }
 
@@ -385,7 +396,8 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
   if (threadIdx.x < 2) blk_any[threadIdx.x] = 0;  // (published by the staging barrier)
 #endif
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
+  const int lane = threadIdx.x & 63;  // (the analysis builds' clocks and probes)
+  (void)lane;
   const int item = blockIdx.x * WPB + wave;
   // The per-pixel int64 fixed-point sums, in the dynamic LDS past the
   // acceleration structure: one set per wave, or (block_flush: the block's
@@ -470,35 +482,100 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
     const float v = (float(j) + jv) * cam_lds[20];  // main.cpp:279
     get_ray<true, float>(lds_camera(cam_lds), u, v, g, ro, rd);
   };
-  // a lane takes job q with its camera ray (or goes idle when the item has
-  // no job q)
-  auto adopt = [&](int q, const V3<float> &ro, const V3<float> &rd, const Xoro &g) {
-    if (q < nq) {
-      o = ro;
-      d = rd;
-      rng = g;
-      pxd = (q - int(__umulhi(uint32_t(q) << 1, m_nv)) * nv) << 24;
-      T = mk(1.f, 1.f, 1.f);
-    } else {
-      active = false;
-    }
-  };
+  auto job_pixel = [&](int q) { return q - int(__umulhi(uint32_t(q) << 1, m_nv)) * nv; };
 
-  // Camera-ray pool: lane L holds the camera ray of job
-  // pbase + L, generated by all 64 lanes at once; a lane whose path ended
-  // takes the next unused slot through ds_bpermute.  The ray generation runs
-  // with every lane busy, once per 64 jobs, instead of once per loop pass
-  // for the few lanes that regenerate.  Same rays bit for bit.
-  V3<float> po, pd;
-  Xoro prng;
-  int pbase = 0, ppos = 64;  // wave-uniform: job of slot 0, next unused slot
-  camera_ray(lane, po, pd, prng);
-  adopt(lane, po, pd, prng);
+  // Path pool: the low slots hold the paths of the last 64
+  // jobs taken from the item, generated by all 64 lanes at once; a lane whose
+  // path ended takes an unused slot (the highest first) through ds_bpermute.
+  // The ray generation runs with every lane busy, once per 64 jobs, instead of
+  // once per loop pass for the few lanes that regenerate.  Same rays bit for bit.
+  // Brute force and BVH: slot L is the camera ray of the L-th of those jobs.
+  // Grid kinds (BATCH): the refill also traces and shades the 64 camera rays
+  // as one coherent pass (one tile at one sample index: the most coherent set
+  // of rays the kernel ever holds), adds the paths that end there (sky,
+  // absorbed, max_depth 1) to the tile's sums at once, and compacts the
+  // survivors into the low slots: a slot is then the path after its first
+  // bounce — origin, direction, generator — and a tag: the pixel in the tile
+  // (bits 0-5), dielectric hit (bit 6), the hit sphere's scene index (7 up).
+  // The adopting lane starts at depth 1 with T = the hit's attenuation, read
+  // again from shade0 (1.0f * x == x: what the first pass would have left).
+  constexpr bool BATCH = acc_grid(ACC);
+  V3<float> po = mk(0.f, 0.f, 0.f), pd = po;
+  Xoro prng{0, 0};
+  int ptag = 0;
+  // wave-uniform: the next job to generate (a multiple of 64) and the slots
+  // still unused (0 .. 64; handed out from the top slot down), in one value,
+  // 2 x the job + the slots: the compiler keeps these loop-carried counters of
+  // the batch kernels in vector registers, so one instead of two
+  int pstate = 0;
+  auto pool_base = [&]() { return __builtin_amdgcn_readfirstlane((pstate >> 7) << 6); };
+  auto pool_left = [&]() { return __builtin_amdgcn_readfirstlane(pstate & 127); };
+#if RTMI_TRACE_PHASES
+  unsigned long long cyc_batch = 0;
+#endif
   auto pull = [](int src4, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src4, __float_as_int(v))); };
   auto pull64 = [](int src4, uint64_t v) {
     const uint32_t lo = uint32_t(__builtin_amdgcn_ds_bpermute(src4, int(uint32_t(v))));
     const uint32_t hi = uint32_t(__builtin_amdgcn_ds_bpermute(src4, int(uint32_t(v >> 32))));
     return (uint64_t(hi) << 32) | lo;
+  };
+  auto push = [](int dst4, float v) { return __int_as_float(__builtin_amdgcn_ds_permute(dst4, __float_as_int(v))); };
+  auto push64 = [](int dst4, uint64_t v) {
+    const uint32_t lo = uint32_t(__builtin_amdgcn_ds_permute(dst4, int(uint32_t(v))));
+    const uint32_t hi = uint32_t(__builtin_amdgcn_ds_permute(dst4, int(uint32_t(v >> 32))));
+    return (uint64_t(hi) << 32) | lo;
+  };
+  // the next 64 jobs into the (empty) pool; every lane of the wave runs this
+  auto refill = [&]() {
+    const int pbase = pool_base();
+    int plive;
+    // the lane index recomputed where it is used, not kept live through the
+    // batch's walk (the register peak of the kernel)
+    auto lane_now = []() {
+      unsigned below = 0;  // (opaque, so that the count is formed anew at each use)
+      asm volatile("" : "+s"(below));
+      return int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, below)));
+    };
+    const int q = pbase + lane_now();
+    const int nvalid = min(64, nq - pbase);  // > 0
+    if constexpr (BATCH) {
+#if RTMI_TRACE_PHASES
+      const unsigned long long cyc_r = __builtin_amdgcn_s_memtime();
+#endif
+      bool survives = false;
+      if (q < nq) {
+        camera_ray(q, po, pd, prng);
+        V3<float> unused_T = mk(1.f, 1.f, 1.f), col = mk(0.f, 0.f, 0.f);
+        int hit = 0;
+        survives = !path_segment<ACC, true>(sc, pairs, a, po, pd, unused_T, hit, prng, col, cnt, segments);
+        const int px = job_pixel(pbase + lane_now());  // (after the walk: not live through it)
+        ptag = px | (hit << 6);
+        if (!survives) {
+          atomicAdd(&acc[px], (unsigned long long)to_fixed(col.x));
+          atomicAdd(&acc[64 + px], (unsigned long long)to_fixed(col.y));
+          atomicAdd(&acc[128 + px], (unsigned long long)to_fixed(col.z));
+        }
+      }
+      nseg = unsigned(__builtin_amdgcn_readfirstlane(int(nseg + unsigned(nvalid))));
+      // survivors to slots 0 .. plive-1 in lane order, the rest behind them:
+      // a permutation, so every lane pushes and every lane receives
+      const unsigned long long m = __ballot(survives);
+      plive = __popcll(m);
+      const int rank = __builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u));
+      const int dst4 = (survives ? rank : plive + lane_now() - rank) << 2;
+      po = mk(push(dst4, po.x), push(dst4, po.y), push(dst4, po.z));
+      pd = mk(push(dst4, pd.x), push(dst4, pd.y), push(dst4, pd.z));
+      prng.s0 = push64(dst4, prng.s0);
+      prng.s1 = push64(dst4, prng.s1);
+      ptag = __builtin_amdgcn_ds_permute(dst4, ptag);
+#if RTMI_TRACE_PHASES
+      cyc_batch += __builtin_amdgcn_s_memtime() - cyc_r;
+#endif
+    } else {
+      camera_ray(q, po, pd, prng);  // (a lane past the item's last job: a ray nobody takes)
+      plive = nvalid;
+    }
+    pstate = __builtin_amdgcn_readfirstlane(2 * (pbase + 64) + plive);
   };
 
 #if RTMI_SYNC_PROBE
@@ -507,8 +584,76 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
   // synchronisation a block-level regrouping of rays would need (DESIGN.md
   // §8.2), without the regrouping.  block_flush launches only (every wave of
   // the block has an item).
+  bool done = true;  // every lane begins by taking a path from the pool
   for (int pass = 0;; ++pass) {
+#else
+  bool done = true;  // every lane begins by taking a path from the pool
+  for (;;) {
+#endif
+#if RTMI_TRACE_PHASES
+    const unsigned long long cyc_h = __builtin_amdgcn_s_memtime(), cyc_batch0 = cyc_batch;
+#endif
+    // Hand-out: the lanes whose path ended (at the start: all) take the pool's
+    // next unused slots by their rank among them; an empty pool is refilled
+    // while the item has jobs — a loop, because a whole batch may die (a sky
+    // tile, max_depth 1) — and the lanes still unserved then go idle.
+    const unsigned long long m = __ballot(done);
+    if (m) {
+      // a lane's rank among the ended lanes minus those served so far: formed
+      // per round from the mask (scalars), so that no rank is a register held
+      // through a refill's walk
+      auto rank_from = [&](int base) {
+        return int(__builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), unsigned(-base))));
+      };
+      const int ndone = __popcll(m);
+      int served = 0;
+      while (served < ndone) {
+        const int pleft = pool_left();
+        if (pleft == 0) {
+          if (pool_base() >= nq) break;
+          refill();
+          continue;
+        }
+        const int take = min(ndone - served, pleft);
+        const int r = rank_from(served);
+        const int src4 = ((pleft - 1 - r) & 63) << 2;  // every lane reads (ds_bpermute reads active lanes only)
+        V3<float> ro, rd;
+        Xoro g;
+        ro = mk(pull(src4, po.x), pull(src4, po.y), pull(src4, po.z));
+        rd = mk(pull(src4, pd.x), pull(src4, pd.y), pull(src4, pd.z));
+        g.s0 = pull64(src4, prng.s0);
+        g.s1 = pull64(src4, prng.s1);
+        int tag = 0;
+        if constexpr (BATCH) tag = __builtin_amdgcn_ds_bpermute(src4, ptag);
+        if (done && r >= 0 && r < take) {
+          o = ro;
+          d = rd;
+          rng = g;
+          if constexpr (BATCH) {
+            const float4 s0 = sh0[tag >> 7];
+            T = (tag & 64) ? mk(1.f, 1.f, 1.f) : mk(s0.y, s0.z, s0.w);  // scatter_fast's attenuation
+            pxd = ((tag & 63) << 24) | 1;
+          } else {
+            T = mk(1.f, 1.f, 1.f);
+            pxd = job_pixel(pool_base() - 64 + pleft - 1 - r) << 24;
+          }
+        }
+        pstate = __builtin_amdgcn_readfirstlane(pstate - take);
+        served = __builtin_amdgcn_readfirstlane(served + take);
+      }
+      // the item has no path left for the lanes still unserved.  (Bitwise, no
+      // branch: a lane-dependent branch here, where the hand-out's uniform
+      // paths join, makes the compiler treat the pool's wave-uniform counters
+      // as per-lane values and keep them in vector registers.)
+      active = active & !(done & (rank_from(served) >= 0));
+      done = false;
+    }
+#if RTMI_TRACE_PHASES
+    const unsigned long long cyc_a = __builtin_amdgcn_s_memtime();
+    cyc_regen += (cyc_a - cyc_h) - (cyc_batch - cyc_batch0);
+#endif
     const unsigned long long live = __ballot(active);
+#if RTMI_SYNC_PROBE
     if (lane == 0 && live) atomicOr(&blk_any[pass & 1], 1);
     __syncthreads();
     const int any_live = blk_any[pass & 1];
@@ -517,56 +662,23 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
     if (!any_live) break;
     if (live == 0) continue;
 #else
-  for (;;) {
-    const unsigned long long live = __ballot(active);
     if (live == 0) break;
 #endif
     nseg = unsigned(__builtin_amdgcn_readfirstlane(int(nseg + unsigned(__popcll(live)))));
-    bool done = false;
     V3<float> col = mk(0.f, 0.f, 0.f);
-#if RTMI_TRACE_PHASES
-    const unsigned long long cyc_a = __builtin_amdgcn_s_memtime();
-#endif
     if (active) {
       done = path_segment<ACC>(sc, pairs, a, o, d, T, pxd, rng, col, cnt, segments);
     }
 #if RTMI_TRACE_PHASES
     const unsigned long long cyc_b = __builtin_amdgcn_s_memtime();
     cyc_iter += cyc_b - cyc_a;  // hit + shading of this pass (wave-level)
-    const bool ramp = pbase + ppos >= nq;  // the item's jobs all handed out: the wave's ramp-down
+    const bool ramp = pool_base() >= nq && pool_left() == 0;  // the item's paths all handed out: the wave's ramp-down
 #endif
-    const unsigned long long m = __ballot(done);
-    if (m) {
-      if (done) {
-        const int px = pxd >> 24;
-        atomicAdd(&acc[px], (unsigned long long)to_fixed(col.x));
-        atomicAdd(&acc[64 + px], (unsigned long long)to_fixed(col.y));
-        atomicAdd(&acc[128 + px], (unsigned long long)to_fixed(col.z));
-      }
-      const int rank = __builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u));
-      // ranks [0, cnt) take slots ppos, ppos + 1, ...: at most two rounds,
-      // the second after a refill for the next 64 jobs (skipped once the
-      // item has none: those lanes go idle)
-      const int cnt = __popcll(m);
-      for (int served = 0; served < cnt;) {
-        if (ppos == 64) {
-          pbase = __builtin_amdgcn_readfirstlane(pbase + 64);
-          ppos = 0;
-          if (pbase < nq) camera_ray(pbase + lane, po, pd, prng);
-        }
-        const int take = min(cnt - served, 64 - ppos);
-        const int r = rank - served;
-        const int src4 = ((ppos + r) & 63) << 2;  // every lane reads (ds_bpermute reads active lanes only)
-        V3<float> ro, rd;
-        Xoro g;
-        ro = mk(pull(src4, po.x), pull(src4, po.y), pull(src4, po.z));
-        rd = mk(pull(src4, pd.x), pull(src4, pd.y), pull(src4, pd.z));
-        g.s0 = pull64(src4, prng.s0);
-        g.s1 = pull64(src4, prng.s1);
-        if (done && r >= 0 && r < take) adopt(pbase + ppos + r, ro, rd, g);
-        ppos = __builtin_amdgcn_readfirstlane(ppos + take);
-        served = __builtin_amdgcn_readfirstlane(served + take);
-      }
+    if (done) {
+      const int px = pxd >> 24;
+      atomicAdd(&acc[px], (unsigned long long)to_fixed(col.x));
+      atomicAdd(&acc[64 + px], (unsigned long long)to_fixed(col.y));
+      atomicAdd(&acc[128 + px], (unsigned long long)to_fixed(col.z));
     }
 #if RTMI_TRACE_PHASES
     const unsigned long long cyc_e = __builtin_amdgcn_s_memtime();
@@ -579,7 +691,12 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
   // waves share the tile) summed in LDS and added once per block at the
   // flush — 30 000 instead of 120 000 single-lane global atomics at config 2
   const bool block_counts = CHUNKED && a.block_flush;
-  if (lane == 0) {
+  // the lane index formed anew here (every lane of the wave is here: the
+  // count of lanes below), so that neither it nor the thread index is kept
+  // live (in scratch) since the accumulator's initialisation
+  int fl = int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+  asm volatile("" : "+v"(fl));
+  if (fl == 0) {
     if (block_counts) {
       blk_seg[wave] = nseg;
     } else {
@@ -587,25 +704,23 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
       if (a.tile_cost) atomicAdd(&a.tile_cost[tile], nseg);
     }
   }
-  flush_counters(cnt, lane, segments);
+  flush_counters(cnt, fl, segments);
 #if RTMI_TRACE_PHASES
   // [1] big spheres + clip/setup, [2] loop passes after the item's last job
   // was taken (ramp-down), [3] cell walk
   cnt.pc.c[0] += cnt.pc.c[1];
   cnt.pc.c[1] = cyc_ramp;
-  if (lane == 0) for (int q = 0; q < 3; ++q) atomicAdd(&segments[1 + q], cnt.pc.c[q]);
-  // wave-level: [4] hit + shading passes, [7] accumulation + regeneration
-  if (lane == 0) { atomicAdd(&segments[4], cyc_iter); atomicAdd(&segments[7], cyc_regen); }
+  if (fl == 0) for (int q = 0; q < 3; ++q) atomicAdd(&segments[1 + q], cnt.pc.c[q]);
+  // wave-level: [4] hit + shading passes, [7] accumulation + hand-out, and
+  // for the batch kernels [5] the pool's batch passes (trace, shade, compact)
+  if (fl == 0) { atomicAdd(&segments[4], cyc_iter); atomicAdd(&segments[7], cyc_regen); }
+  if (BATCH && fl == 0) atomicAdd(&segments[5], cyc_batch);
 #endif
   RTMI_TRACE_END(1, nseg)
-  // the lane index recomputed here, not kept live (in scratch) since the
-  // accumulator's initialisation
-  int fl = int(threadIdx.x & 63u);
-  asm volatile("" : "+v"(fl));
   if constexpr (CHUNKED) {
     if (a.block_flush) {  // block-uniform; no wave of this block returned early
       __syncthreads();
-      if (block_counts && threadIdx.x == 0) {
+      if (block_counts && wave == 0 && fl == 0) {
         unsigned bseg = 0;
 #pragma unroll
         for (int w = 0; w < WPB; ++w) bseg += blk_seg[w];

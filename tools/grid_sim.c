@@ -25,6 +25,9 @@
  *
  *   gcc -O2 -o /tmp/grid_sim tools/grid_sim.c -lm && /tmp/grid_sim tests/golden/scene_final.txt [spp] [stride]
  *   (BEHIND_CULL=1: candidates without the spheres a ray leaves from outside, as RTMI_BEHIND_CULL)
+ *   (PRIMARY_BATCH=1: only the primary-batch model, DESIGN.md section 4.5: camera segments in path order
+ *   in groups of 64 and secondary segments in groups of 64 against today's mixed groups, with 0 / 40 / 80 /
+ *   120 extra instructions per batch pass; profiles/r07/primary_batch/grid_sim_primary_batch.txt)
  */
 #include <math.h>
 #include <stdio.h>
@@ -559,6 +562,53 @@ int main(int argc, char **argv) {
     printf("\n");
   }
   if (getenv("CI_REST")) CI_REST = atof(getenv("CI_REST"));
+  if (getenv("PRIMARY_BATCH")) {
+    /* Primary batches: per tile the camera segments in
+     * path order in groups of 64 (one pool refill each: one tile at one
+     * sample index) and the secondary segments, in their shuffled order, in
+     * groups of 64; against today's mixed groups.  A pass costs CI_REST + its
+     * walk; a batch pass E more (the survivors' compaction, the adopting
+     * lanes' extra gather). */
+    double mixed = 0, mwalk = 0, mpass = 0, mcell = 0, msph = 0;
+    double pwalk = 0, ppass = 0, pcell = 0, psph = 0, swalk = 0, spass = 0, scell = 0, ssph = 0;
+    int *pr = malloc(nseg * sizeof(int)), *se = malloc(nseg * sizeof(int));
+#define GROUP_SHAPE(ids_, nl_, cells_, sph_) do { int maxc_ = 0; \
+      for (int l_ = 0; l_ < (nl_); l_++) if (W[(ids_)[l_]].nc > maxc_) maxc_ = W[(ids_)[l_]].nc; \
+      (cells_) += maxc_; \
+      for (int c_ = 0; c_ < maxc_; c_++) { int m_ = 0; \
+        for (int l_ = 0; l_ < (nl_); l_++) { const Walk *w_ = &W[(ids_)[l_]]; if (c_ < w_->nc && w_->lens[c_] > m_) m_ = w_->lens[c_]; } \
+        (sph_) += m_; } } while (0)
+    for (int t = 0; t < ntiles; t++) {
+      int np = 0, ns = 0;
+      for (int i = tile_start[t]; i < tile_start[t + 1]; i++) { if (segs[i].depth == 0) pr[np++] = i; else se[ns++] = i; }
+      for (int i = 1; i < np; i++) {  /* path order (generation order: sample-major over the tile's pixels) */
+        const int x = pr[i]; int j = i - 1;
+        while (j >= 0 && segs[pr[j]].path > segs[x].path) { pr[j + 1] = pr[j]; j--; }
+        pr[j + 1] = x;
+      }
+      for (int i = tile_start[t]; i < tile_start[t + 1]; i += 64) {
+        const int nl = tile_start[t + 1] - i < 64 ? tile_start[t + 1] - i : 64;
+        for (int l = 0; l < nl; l++) ids[l] = i + l;
+        const double c = walk_instr(ids, nl, NULL);
+        mixed += CI_REST + c; mwalk += c; mpass++; GROUP_SHAPE(ids, nl, mcell, msph);
+      }
+      for (int i = 0; i < np; i += 64) { const int nl = np - i < 64 ? np - i : 64;
+        pwalk += walk_instr(pr + i, nl, NULL); ppass++; GROUP_SHAPE(pr + i, nl, pcell, psph); }
+      for (int i = 0; i < ns; i += 64) { const int nl = ns - i < 64 ? ns - i : 64;
+        swalk += walk_instr(se + i, nl, NULL); spass++; GROUP_SHAPE(se + i, nl, scell, ssph); }
+    }
+    printf("  primary batches: passes today %.0f; batch %.0f (%.3f of the new passes) + secondary-only %.0f\n", mpass, ppass,
+           ppass / (ppass + spass), spass);
+    printf("  walk instr per wave-pass | wave cells / spheres: today (mixed) %.1f | %.2f / %.2f; primary batch %.1f | %.2f / %.2f; "
+           "secondary-only %.1f | %.2f / %.2f\n", mwalk / mpass, mcell / mpass, msph / mpass, pwalk / ppass, pcell / ppass,
+           psph / ppass, swalk / spass, scell / spass, ssph / spass);
+    printf("  the walk alone: %.3f of today's\n", (pwalk + swalk) / mwalk);
+    for (double E = 0; E <= 120; E += 40)
+      printf("  hand-over %3.0f instr per batch pass: all passes %.3f of today's instructions\n", E,
+             (CI_REST * (ppass + spass) + E * ppass + pwalk + swalk) / mixed);
+    free(pr); free(se);
+    return 0;
+  }
   if (getenv("QUEUE_ONLY")) {
     build_paths();
     const double Es[4] = {0, 60, 100, 140};
