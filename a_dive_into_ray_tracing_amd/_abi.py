@@ -128,6 +128,10 @@ SIGNATURES = {
     "rt_nw_moving_sphere": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "rt_nw_rect": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_double] * 5 + [C.c_int32]),
     "rt_nw_box": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32]),
+    "rt_nw_triangle": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int32]),
+    "rt_nw_mesh": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, C.c_int32, _dp, C.c_int32, _ip, C.c_int32]),
+    "rt_nw_load_obj": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _ip]),
+    "rt_nw_scene_obj_stage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
     "rt_nw_constant_medium": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     "rt_nw_medium_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rt_nw_group": (C.c_int, [C.c_void_p, _ip, C.c_int32]),
@@ -157,6 +161,7 @@ SIGNATURES = {
     "rt_ctx_grid_info": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     "rt_nw_ctx_last_segments": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_nw_ctx_last_kernel": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_ctx_last_staging": (C.c_int, [C.c_void_p, _ip]),
     "rt_nw_debug_trace": (C.c_int, [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 3 + [C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32, _ip]),
     "rt_nw_debug_hits": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _ip]),
 }

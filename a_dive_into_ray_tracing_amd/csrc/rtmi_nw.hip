@@ -173,7 +173,7 @@ __device__ __forceinline__ void stage_scene(const View &sc) {
 // One work item = (8x8 tile, <= chunk samples) on one wave: lanes pull
 // (pixel, sample) jobs from the item's queue and regenerate paths as theirs
 // end; sums in the wave's LDS accumulator, then one global add per pixel.
-template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false>
+template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false, bool TRI = false>
 __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item, int lane,
                                          unsigned long long (&acc)[3][64], unsigned long long *__restrict__ accum,
                                          float *__restrict__ out, unsigned &nseg, const float *cl) {
@@ -253,8 +253,8 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
       const uint64_t seg_key = !S && sc.has_media ? rng.next() : 0ull;
       float t;
       int face;
-      const int32_t k = GRID ? hit_world_nw_grid<S>(sc, o, d, time, seg_key, t, face, &cnt)
-                             : hit_world_nw<LDS_NODES, LDS_OBJS>(sc, o, d, time, seg_key, t, face, &cnt);
+      const int32_t k = GRID ? hit_world_nw_grid<S, TRI>(sc, o, d, time, seg_key, t, face, &cnt)
+                             : hit_world_nw<LDS_NODES, LDS_OBJS, TRI>(sc, o, d, time, seg_key, t, face, &cnt);
 #if RTMI_NW_PHASES
       pb = __builtin_amdgcn_s_memtime();
 #endif
@@ -262,7 +262,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
         col = mk(T.x * sc.bg[0], T.y * sc.bg[1], T.z * sc.bg[2]);
         done = true;
       } else {
-        const Rec rec = S || k < sc.nobj ? make_rec<S>(sc, sc.obj[k], o, d, time, t, face)
+        const Rec rec = S || k < sc.nobj ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face)
                                          : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
         const Mat m = sc.mat[rec.mat];
         V at, nd;
@@ -338,7 +338,8 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
   if (lane == 0) atomicAdd(segments, (unsigned long long)nseg);  // the wave's world.hit calls (wave-uniform)
 }
 
-template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID>
+// TRI (last parameter of both kernels): the scene holds triangles (hit_object)
+template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool TRI = false>
 __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, unsigned long long *__restrict__ accum,
                                                              float *__restrict__ out,
                                                              unsigned long long *__restrict__ segments) {
@@ -352,14 +353,14 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
   stage_scene<LDS_NODES, LDS_OBJS, GRID>(sc);  // block barrier inside: before any wave leaves
   if (item >= a.n_items) return;         // wave-uniform
   unsigned nseg = 0;
-  run_item<CHUNKED, LDS_NODES, LDS_OBJS, GRID>(sc, a, item, lane, acc[wave], accum, out, nseg, cam_lds);
+  run_item<CHUNKED, LDS_NODES, LDS_OBJS, GRID, false, TRI>(sc, a, item, lane, acc[wave], accum, out, nseg, cam_lds);
   add_segments(nseg, lane, segments);
 }
 
 #ifndef RTMI_NW_PERSIST_GRID_PER_EU
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
-template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false>
+template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, bool TRI = false>
 __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : RTMI_NW_PERSIST_PER_EU)) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
     if (lane == 0) it = atomicAdd(counter, 1u);
     it = __builtin_amdgcn_readfirstlane(__shfl(it, 0));
     if (int(it) >= a.n_items) break;
-    run_item<CHUNKED, true, LDS_OBJS, GRID, S>(sc, a, int(it), lane, acc[wave], accum, out, nseg, cam_lds);
+    run_item<CHUNKED, true, LDS_OBJS, GRID, S, TRI>(sc, a, int(it), lane, acc[wave], accum, out, nseg, cam_lds);
   }
   add_segments(nseg, lane, segments);
 }
@@ -402,14 +403,14 @@ __global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, i
     const uint64_t seg_key = sc.has_media ? rng.next() : 0ull;
     float t;
     int face;
-    const int32_t k = hit_world_nw<false, false>(sc, o, d, time, seg_key, t, face, &tcnt);
+    const int32_t k = hit_world_nw<false, false, true>(sc, o, d, time, seg_key, t, face, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
     r[7] = __int_as_float(k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj]);
     r[8] = r[9] = r[10] = 0.f;
     r[11] = __int_as_float(face);
     if (k < 0) break;
-    const Rec rc = k < sc.nobj ? make_rec(sc, sc.obj[k], o, d, time, t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
+    const Rec rc = k < sc.nobj ? make_rec<false, true>(sc, sc.obj[k], o, d, time, t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
     V at, nd;
@@ -442,8 +443,8 @@ __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *_
   NwCount cnt{0, 0, 0, 0};
   float t;
   int face;
-  const int32_t k = GRID ? hit_world_nw_grid<false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
-                         : hit_world_nw<false, false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
+  const int32_t k = GRID ? hit_world_nw_grid<false, true>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
+                         : hit_world_nw<false, false, true>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
   out_id[i] = k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_face[i] = face;
@@ -491,6 +492,7 @@ struct rt_nw_ctx {
   int32_t accel = RT_NW_ACCEL_AUTO;
   float bg[3] = {0.f, 0.f, 0.f};
   int32_t has_media = 0;
+  int32_t has_tri = 0;
   unsigned long long *accum = nullptr;
   size_t accum_cap = 0;
   float *scratch = nullptr;
@@ -506,11 +508,15 @@ struct rt_nw_ctx {
   bool simple = false;
   bool simple_ok = !(std::getenv("RTMI_NW_SIMPLE") && std::getenv("RTMI_NW_SIMPLE")[0] == '0');
   int32_t persist_blocks_simple = 0;
+  // RTMI_NW_PERSIST=0: render with the one-shot grid-of-blocks kernels (A/B
+  // and tests; the same image), read when the context is created
+  bool persist_ok = !(std::getenv("RTMI_NW_PERSIST") && std::getenv("RTMI_NW_PERSIST")[0] == '0');
   int32_t cus = 0;  // compute units of the device
   // resident blocks per CU of a persistent launch, by (kernel, dynamic LDS
   // bytes): the occupancy query repeated with the bytes the launch stages
   std::vector<std::pair<std::pair<const void *, size_t>, int32_t>> occupancy;
   int32_t last_kernel[4] = {0, 0, 0, 0};  // rt_nw_ctx_last_kernel
+  int32_t last_staging[2] = {0, 0};       // rt_nw_ctx_last_staging
   // samples per work item forced by RTMI_NW_CHUNK (A/B only; 0 = automatic),
   // read when the context is created
   int32_t env_chunk = std::getenv("RTMI_NW_CHUNK") ? std::atoi(std::getenv("RTMI_NW_CHUNK")) : 0;
@@ -640,7 +646,7 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   const int32_t nt = int32_t(ds.tex.size()), nm = int32_t(ds.mat.size()), ni = int32_t(ds.inst.size());
   const int32_t np = int32_t(ds.perlin_perm.size() / (3 * kPerlinN)), nim = int32_t(ds.image.size());
   for (const Obj &o : ds.obj)
-    if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere || o.kind > kBox || o.aux < 0 ||
+    if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere || (o.kind > kBox && o.kind != kTriangle) || o.aux < 0 ||
         o.aux > int32_t(ds.med.size()))
       return set_error(RT_EINVAL, "rt_nw: object with bad material/instance/kind");
   for (const Obj &o : ds.med) {
@@ -739,6 +745,8 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   ctx->ntex = nt;
   for (int c = 0; c < 3; ++c) ctx->bg[c] = ds.background[c];
   ctx->has_media = ds.has_media ? 1 : 0;
+  ctx->has_tri = 0;
+  for (const Obj &o : ds.obj) ctx->has_tri |= o.kind == kTriangle ? 1 : 0;
   bool simple = ds.med.empty();
   for (const Obj &o : ds.obj) simple = simple && o.inst < 0 && (o.kind == kSphere || o.kind == kMovingSphere);
   for (const Tex &t : ds.tex)
@@ -766,7 +774,7 @@ int32_t accel_used(const rt_nw_ctx *c) {
   // the grid is staged whole: by the persistent kernel (one block per CU)
   // when it runs, else by the grid kernel's per-block budget; a grid that
   // fits neither renders with the BVH
-  const bool persist = RTMI_NW_PERSIST && c->persist_blocks_grid > 0;
+  const bool persist = RTMI_NW_PERSIST && c->persist_ok && c->persist_blocks_grid > 0;
   const bool fits = c->grid_ok && grid_bytes(c) <= (persist ? kPLdsBudget : kLdsBudget);
   if (c->accel == RT_NW_ACCEL_GRID) return fits ? RT_NW_ACCEL_GRID : RT_NW_ACCEL_BVH;
   if (c->accel == RT_NW_ACCEL_BVH) return RT_NW_ACCEL_BVH;
@@ -824,7 +832,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   const size_t node_bytes = size_t(ctx->nnodes) * 32, obj_bytes = size_t(ctx->nobj) * (sizeof(DevObj) + 4);
   const bool use_grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
   const size_t gbytes = use_grid ? grid_bytes(ctx) : 0;
-  const bool persist = RTMI_NW_PERSIST && (use_grid ? ctx->persist_blocks_grid > 0 : ctx->persist_blocks > 0) &&
+  const bool persist = RTMI_NW_PERSIST && ctx->persist_ok && (use_grid ? ctx->persist_blocks_grid > 0 : ctx->persist_blocks > 0) &&
                        (use_grid || (ctx->nnodes > 0 && node_bytes <= kPLdsBudget));
   // the spheres-only instantiation of the persistent grid kernel
   const bool simple = persist && use_grid && ctx->simple && ctx->simple_ok && ctx->persist_blocks_simple > 0;
@@ -864,14 +872,18 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
                                : lds_objs ? node_bytes + obj_bytes : lds_nodes ? node_bytes : 0;
   // the kernel that will run, its static LDS beside the staged bytes, and
   // (persistent) how many of its blocks stay resident with those bytes
-  const void *kfn = simple ? (const void *)render_persistent<true, true, true, true>
-                    : persist && use_grid ? (const void *)render_persistent<true, true, true>
-                    : persist && p_objs ? (const void *)render_persistent<true, true, false>
-                    : persist ? (const void *)render_persistent<true, false, false>
-                    : g_grid ? (const void *)render_kernel<true, false, false, true>
-                    : lds_objs ? (const void *)render_kernel<true, true, true, false>
-                    : lds_nodes ? (const void *)render_kernel<true, true, false, false>
-                                : (const void *)render_kernel<true, false, false, false>;
+  auto kernel_of = [&](auto tri) -> const void * {
+    constexpr bool T = decltype(tri)::value;
+    return simple                ? (const void *)render_persistent<true, true, true, true>
+           : persist && use_grid ? (const void *)render_persistent<true, true, true, false, T>
+           : persist && p_objs   ? (const void *)render_persistent<true, true, false, false, T>
+           : persist             ? (const void *)render_persistent<true, false, false, false, T>
+           : g_grid              ? (const void *)render_kernel<true, false, false, true, T>
+           : lds_objs            ? (const void *)render_kernel<true, true, true, false, T>
+           : lds_nodes           ? (const void *)render_kernel<true, true, false, false, T>
+                                 : (const void *)render_kernel<true, false, false, false, T>;
+  };
+  const void *kfn = ctx->has_tri ? kernel_of(std::true_type{}) : kernel_of(std::false_type{});
   {
     hipFuncAttributes fa;
     HIP_TRY(hipFuncGetAttributes(&fa, kfn));
@@ -909,24 +921,30 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   ctx->last_kernel[1] = use_grid ? 1 : 0;
   ctx->last_kernel[2] = simple ? 1 : 0;
   ctx->last_kernel[3] = a.chunk;
-  auto launch = [&](auto chunked) {
-    constexpr bool C = decltype(chunked)::value;
+  ctx->last_staging[0] = !use_grid && (persist || lds_nodes) ? 1 : 0;
+  ctx->last_staging[1] = use_grid || (persist ? p_objs : lds_objs) ? 1 : 0;
+  auto launch_t = [&](auto chunked, auto tri) {
+    constexpr bool C = decltype(chunked)::value, T = decltype(tri)::value;
     if (simple)
       hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (persist && use_grid)
-      hipLaunchKernelGGL((render_persistent<C, true, true>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+      hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (persist && p_objs)
-      hipLaunchKernelGGL((render_persistent<C, true, false>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+      hipLaunchKernelGGL((render_persistent<C, true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (persist)
-      hipLaunchKernelGGL((render_persistent<C, false, false>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+      hipLaunchKernelGGL((render_persistent<C, false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (g_grid)
-      hipLaunchKernelGGL((render_kernel<C, false, false, true>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
     else if (lds_objs)
-      hipLaunchKernelGGL((render_kernel<C, true, true, false>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
     else if (lds_nodes)
-      hipLaunchKernelGGL((render_kernel<C, true, false, false>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
     else
-      hipLaunchKernelGGL((render_kernel<C, false, false, false>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
+  };
+  auto launch = [&](auto chunked) {
+    if (ctx->has_tri) launch_t(chunked, std::true_type{});
+    else launch_t(chunked, std::false_type{});
   };
   if (a.nch > 1) {
     const size_t nv = size_t(valid) * W * 3;
@@ -1072,6 +1090,13 @@ RTMI_EXPORT int rt_nw_debug_phases(uint64_t *out4) {
 RTMI_EXPORT int rt_nw_ctx_last_kernel(rt_nw_ctx *ctx, int32_t *out4) {
   if (!ctx || !out4) return set_error(RT_EINVAL, "null");
   for (int q = 0; q < 4; ++q) out4[q] = ctx->last_kernel[q];
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_ctx_last_staging(rt_nw_ctx *ctx, int32_t *out2) {
+  if (!ctx || !out2) return set_error(RT_EINVAL, "null");
+  out2[0] = ctx->last_staging[0];
+  out2[1] = ctx->last_staging[1];
   return RT_OK;
 }
 

@@ -7,6 +7,13 @@
 //   rtmi_nw_render [--scene 1..8|final|cornell_box|...] [--width W] [--height H]
 //                  [--spp S] [--depth D] [--seed N] [--texture FILE.ppm]
 //                  [--out FILE|-] [--p6] [--rtl]
+//   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--width W] ...
+//
+// --obj (exclusive with --scene) renders a Wavefront OBJ mesh
+// (rt_nw_scene_obj_stage): scaled and centred into the box [-1, 1] x [0, 2] x
+// [-1, 1] on a checker ground, one 3 x 3 light of emission 6 at y = 5,
+// background (0.05, 0.07, 0.12), camera from (3.2, 2.4, 4.8) at (0, 1, 0),
+// vfov 30, no aperture.
 //
 // --texture is the earth image as a binary PPM (P6; the reference decodes
 // earthmap.jpeg with stb_image, main.cu:497-510 — convert it once, e.g. with
@@ -60,7 +67,8 @@ static bool read_p6(const char *path, std::vector<uint8_t> &px, int &w, int &h) 
 }
 
 int main(int argc, char **argv) {
-  std::string scene = "8", out = "-", texture;
+  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian";
+  bool scene_given = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0;
   unsigned long long seed = 1984;
   for (int a = 1; a < argc; a++) {
@@ -68,7 +76,9 @@ int main(int argc, char **argv) {
       if (a + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", f); std::exit(2); }
       return argv[++a];
     };
-    if (!std::strcmp(argv[a], "--scene")) scene = need("--scene");
+    if (!std::strcmp(argv[a], "--scene")) { scene = need("--scene"); scene_given = true; }
+    else if (!std::strcmp(argv[a], "--obj")) obj = need("--obj");
+    else if (!std::strcmp(argv[a], "--obj-mat")) obj_mat = need("--obj-mat");
     else if (!std::strcmp(argv[a], "--width")) W = std::atoi(need("--width"));
     else if (!std::strcmp(argv[a], "--height")) H = std::atoi(need("--height"));
     else if (!std::strcmp(argv[a], "--spp")) spp = std::atoi(need("--spp"));
@@ -80,7 +90,12 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--rtl")) rtl = 1;
     else {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
-                           "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n", argv[0]);
+                           "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
+                           "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--width W] [--height H] ...\n"
+                           "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
+                           "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
+                           "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n",
+                   argv[0], argv[0]);
       return 2;
     }
   }
@@ -89,7 +104,11 @@ int main(int argc, char **argv) {
   int which = std::atoi(scene.c_str());
   for (int k = 1; k <= 8; ++k)
     if (scene == names[k]) which = k;
-  if (which < 1 || which > 8) { std::fprintf(stderr, "unknown scene %s\n", scene.c_str()); return 2; }
+  if (!obj.empty() && scene_given) { std::fprintf(stderr, "--scene and --obj are exclusive\n"); return 2; }
+  const int obj_kind = obj_mat == "lambertian" ? RT_NW_LAMBERTIAN : obj_mat == "metal" ? RT_NW_METAL : obj_mat == "glass" ? RT_NW_DIELECTRIC : -1;
+  if (obj_kind < 0) { std::fprintf(stderr, "unknown --obj-mat %s (lambertian, metal, glass)\n", obj_mat.c_str()); return 2; }
+  if (obj.empty() && (which < 1 || which > 8)) { std::fprintf(stderr, "unknown scene %s\n", scene.c_str()); return 2; }
+  if (!obj.empty()) which = 0;
   if (H < 0) H = W;  // aspect_ratio = 1.0, main.cu:517-519
   std::vector<uint8_t> img;
   int iw = 0, ih = 0;
@@ -102,9 +121,12 @@ int main(int argc, char **argv) {
   rt_nw_camera cam;
   int rc;
   if ((rc = rt_nw_scene_create(&s))) return die("rt_nw_scene_create", rc);
-  if ((rc = rt_nw_scene_preset(s, which, img.empty() ? nullptr : img.data(), iw, ih, double(W) / H,
-                               rtl ? RT_NW_ARGS_RTL : 0, &cam)))
+  if (!obj.empty()) {
+    if ((rc = rt_nw_scene_obj_stage(s, obj.c_str(), obj_kind, double(W) / H, &cam, nullptr))) return die("rt_nw_scene_obj_stage", rc);
+  } else if ((rc = rt_nw_scene_preset(s, which, img.empty() ? nullptr : img.data(), iw, ih, double(W) / H,
+                                      rtl ? RT_NW_ARGS_RTL : 0, &cam))) {
     return die("rt_nw_scene_preset", rc);
+  }
   rt_nw_ctx *ctx = nullptr;
   if ((rc = rt_nw_ctx_create(0, &ctx))) return die("rt_nw_ctx_create", rc);
   if ((rc = rt_nw_ctx_set_scene(ctx, s))) return die("rt_nw_ctx_set_scene", rc);

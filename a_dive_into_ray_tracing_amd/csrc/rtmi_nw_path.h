@@ -287,6 +287,102 @@ __device__ __forceinline__ int hit_box_inv(V o, V d, V inv, const float4 p0, con
   return face;
 }
 
+// ---------------------------------------------------------------------------
+// triangle (kTriangle): the watertight test of Woop, Benthin and Wald
+// ("Watertight Ray/Triangle Intersection", JCGT 2(1), 2013), two-sided.
+// THE SPECIFICATION (tests/native/nw_mesh_ref.cpp restates it operation for
+// operation; every product and sum below is one float operation, no fmaf):
+//  ray constants, from the direction d of the ray the triangle is tested
+//  with (the world ray, or the local ray of an instanced triangle):
+//   kz = 0; if |d.y| > |d[kz]| kz = 1; if |d.z| > |d[kz]| kz = 2   (ties: lowest axis)
+//   kx = (kz + 1) % 3, ky = (kx + 1) % 3; if d[kz] < 0 swap kx, ky
+//   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz]         (IEEE divisions)
+//  test:
+//   A = v0 - o, B = v1 - o, C = v2 - o                              (per component)
+//   Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz]; likewise B, C
+//   U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax
+//   if U == 0 or V == 0 or W == 0, all three again in double from the float
+//    operands, rounded to float: U = float(double(Cx) * double(By) -
+//    double(Cy) * double(Bx)) etc. (the products are exact in double, so the
+//    sign of the difference is the true sign)
+//   miss if (U < 0 or V < 0 or W < 0) and (U > 0 or V > 0 or W > 0)
+//   det = (U + V) + W; miss if det == 0
+//   Az = Sz * A[kz], Bz = Sz * B[kz], Cz = Sz * C[kz]
+//   T = ((U * Az) + (V * Bz)) + (W * Cz)
+//   t = T / det (IEEE division); hit iff t >= 0.001f — which holds only when
+//    T has det's sign; no upper bound (the caller's closest rule applies it)
+//  record (make_rec): p = o + t d by at3; n = c * (1 / sqrt(dot3(c, c))) with
+//   c = cross(v1 - v0, v2 - v0) as products and differences (c.x = e1.y * e2.z
+//   - e1.z * e2.y, ...); u = V / det, v = W / det from the same U, V, W, det
+//   recomputed (the barycentric weights of v1 and v2; the kernel evaluates
+//   them only when the material's texture reads u, v).
+//  never hit: a triangle whose vertices are collinear — cross(v1 - v0, v2 -
+//   v0) evaluated in double from the float vertices (differences, products,
+//   differences) is the zero vector: it has no normal.  The scene builder
+//   keeps it out of the BVH and the grid, so no kernel tests it.
+// Watertight: the two triangles of an edge shear the same two vertices with
+// the same constants, so their edge functions over it are the same products
+// and one difference with the operands exchanged — exact negatives; the ray
+// is inside one of them or, when the value is 0, the double evaluation gives
+// its exact sign.  Two-sided: either sign pattern of (U, V, W) hits.
+// ---------------------------------------------------------------------------
+struct TriRay {
+  float sx, sy, sz;
+};
+__device__ __forceinline__ float sel3(V a, int k) { return k == 0 ? a.x : k == 1 ? a.y : a.z; }
+// kz | (d[kz] < 0) << 2
+__device__ __forceinline__ int tri_axes(V d) {
+  int kz = 0;
+  float m = __builtin_fabsf(d.x);
+  if (__builtin_fabsf(d.y) > m) { kz = 1; m = __builtin_fabsf(d.y); }
+  if (__builtin_fabsf(d.z) > m) kz = 2;
+  return kz | (sel3(d, kz) < 0.0f ? 4 : 0);
+}
+// a[kx], a[ky], a[kz] by selects (no dynamic register indexing)
+__device__ __forceinline__ V tri_permute(V a, int axes) {
+  const int kz = axes & 3;
+  const V r = kz == 0 ? mk(a.y, a.z, a.x) : kz == 1 ? mk(a.z, a.x, a.y) : a;
+  return (axes & 4) ? mk(r.y, r.x, r.z) : r;
+}
+__device__ __forceinline__ TriRay tri_ray(V d) {
+  const V p = tri_permute(d, tri_axes(d));
+  return TriRay{p.x / p.z, p.y / p.z, drcp(p.z)};  // (drcp: the IEEE 1 / x)
+}
+template <class O> __device__ __forceinline__ void tri_vertices(const O &ob, V &v0, V &v1, V &v2) {
+  v0 = mk(ob.g0[0], ob.g0[1], ob.g0[2]);
+  v1 = mk(ob.g0[3], ob.g1[0], ob.g1[1]);
+  v2 = mk(ob.g1[2], ob.g1[3], time1_of(ob));
+}
+// U, V, W, det and T of the specification; false: a miss by the sign rule or det == 0
+__device__ __forceinline__ bool tri_edges(V o, int axes, TriRay s, V v0, V v1, V v2, float &U, float &Vv, float &W,
+                                          float &det, float &T) {
+  const V A = tri_permute(sub3(v0, o), axes), B = tri_permute(sub3(v1, o), axes), C = tri_permute(sub3(v2, o), axes);
+  const float Ax = A.x - s.sx * A.z, Ay = A.y - s.sy * A.z;
+  const float Bx = B.x - s.sx * B.z, By = B.y - s.sy * B.z;
+  const float Cx = C.x - s.sx * C.z, Cy = C.y - s.sy * C.z;
+  U = Cx * By - Cy * Bx;
+  Vv = Ax * Cy - Ay * Cx;
+  W = Bx * Ay - By * Ax;
+  if (U == 0.0f || Vv == 0.0f || W == 0.0f) {  // (rare: only these lanes run the f64 code)
+    U = float(double(Cx) * double(By) - double(Cy) * double(Bx));
+    Vv = float(double(Ax) * double(Cy) - double(Ay) * double(Cx));
+    W = float(double(Bx) * double(Ay) - double(By) * double(Ax));
+  }
+  det = (U + Vv) + W;
+  const bool neg = (U < 0.0f) | (Vv < 0.0f) | (W < 0.0f), pos = (U > 0.0f) | (Vv > 0.0f) | (W > 0.0f);
+  const float Az = s.sz * A.z, Bz = s.sz * B.z, Cz = s.sz * C.z;
+  T = ((U * Az) + (Vv * Bz)) + (W * Cz);
+  return !(neg & pos) & (det != 0.0f);
+}
+__device__ __forceinline__ bool hit_triangle(V o, V d, TriRay s, V v0, V v1, V v2, float &t) {
+  float U, Vv, W, det, T;
+  const bool in = tri_edges(o, tri_axes(d), s, v0, v1, v2, U, Vv, W, det, T);
+  const float tt = T / det;
+  const bool hit = in & (tt >= 0.001f);
+  t = hit ? tt : t;
+  return hit;
+}
+
 // a medium's boundary (sphere, moving sphere or box) over (tmin, tmax)
 __device__ __forceinline__ bool hit_boundary(const Obj &ob, V o, V d, float time, float tmin, float tmax, float &t) {
   const int bk = ob.aux & 255;
@@ -361,23 +457,36 @@ __device__ __forceinline__ float medium_uniform(uint64_t seg_key, int32_t id, in
 // (sphere 18, moving sphere 30, rectangle 6, box 36, +15 for an instance's
 // ray transform, a medium 2 x its boundary + 4) plus 25 per BVH node slab
 // test or grid-box clip and 5 per grid cell step — and the visits.
+// A triangle (not in bench.py's table: no benchmark scene has one) counts 47,
+// from hit_triangle's sequence: 9 (three vertices minus the origin) + 12 (six
+// shears: a multiply and a subtract each) + 9 (three edge functions: two
+// multiplies, one subtract) + 6 (the sign rule's compares) + 2 (det) + 8
+// (three depths, T) + 1 (the division); the ray constants are per segment
+// and not counted, and an instanced triangle's own (two divisions, one
+// reciprocal) make its transform 18 instead of 15.
 struct NwCount {
   unsigned long long flop;
   unsigned nodes, objects, cells;
 };
 __device__ __forceinline__ unsigned nw_test_flop(int kind, bool inst) {
-  const unsigned f = kind == kSphere ? 18u : kind == kMovingSphere ? 30u : kind == kBox ? 36u : 6u;
-  return f + (inst ? 15u : 0u);
+  const unsigned f = kind == kSphere ? 18u : kind == kMovingSphere ? 30u : kind == kBox ? 36u : kind == kTriangle ? 47u : 6u;
+  return f + (inst ? (kind == kTriangle ? 18u : 15u) : 0u);
 }
 
 // One non-medium object's hit (world ray in; t_min = 0.001, no upper bound:
 // the caller applies the order-independent closest rule).  face: box side.
-// invw = 1/dw per axis of the world ray (hit_rect_inv).
+// invw = 1/dw per axis of the world ray (hit_rect_inv); trw = the world ray's
+// triangle shears Sx, Sy (tri_ray; its Sz is invw's kz component: the same
+// IEEE 1/d), computed per segment.
+// TRI: the scene holds triangles.  Scenes without them run the TRI = false
+// instantiations, the kernels as they were before triangles existed (the
+// triangle test inside the 64-VGPR BVH kernels cost the final scene 15%,
+// profiles/mesh/README.md).
 // S: a spheres-only scene (rt_nw_ctx_set_scene's check: spheres and moving
 // spheres, no instances, no media, solid and checker textures): the other
 // kinds' code is compiled out — the same arithmetic for the kinds that remain.
-template <bool S = false>
-__device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V ow, V dw, V invw, float time,
+template <bool S = false, bool TRI = false>
+__device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V ow, V dw, V invw, float2 trw, float time,
                                            float &t, int &face) {
   if constexpr (S) {
     if ((ob.ka & 255) == kSphere) return hit_sphere(ow, dw, mk(ob.g0[0], ob.g0[1], ob.g0[2]), ob.g0[3], 0.001f, INFINITY, t);
@@ -388,6 +497,16 @@ __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V o
   if (local) to_local(sc.inst[ob.inst], o, d);
   const float tmin = 0.001f;
   const int kind = ob.ka & 255;
+  if constexpr (TRI) {
+    if (kind == kTriangle) {
+      V v0, v1, v2;
+      tri_vertices(ob, v0, v1, v2);
+      TriRay s;
+      if (local) s = tri_ray(d);
+      else s = TriRay{trw.x, trw.y, sel3(invw, tri_axes(d) & 3)};
+      return hit_triangle(o, d, s, v0, v1, v2, t);
+    }
+  }
   switch (kind) {
     case kSphere: return hit_sphere(o, d, mk(ob.g0[0], ob.g0[1], ob.g0[2]), ob.g0[3], tmin, INFINITY, t);
     case kMovingSphere: return hit_moving(o, d, moving_center(ob, time), ob.g0[3], tmin, INFINITY, t);
@@ -401,6 +520,14 @@ __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V o
       return face >= 0;
     }
   }
+}
+// the world ray's Sx, Sy for hit_object<S, TRI>
+template <bool TRI> __device__ __forceinline__ float2 tri_world(V d) {
+  if constexpr (TRI) {
+    const TriRay s = tri_ray(d);
+    return make_float2(s.sx, s.sy);
+  }
+  return make_float2(0.f, 0.f);
 }
 
 // Closest hit of a segment.  1. Media, in insertion order:
@@ -416,7 +543,7 @@ __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V o
 // LDS layout (dynamic shared memory): nodes lo[nnodes], hi[nnodes]; then, when
 // they fit too, the objects (4 float4 each) and their insertion indices.
 extern __shared__ float4 nw_nodes_lds[];
-template <bool LDS_NODES, bool LDS_OBJS>
+template <bool LDS_NODES, bool LDS_OBJS, bool TRI = false>
 __device__ __forceinline__ int32_t hit_world_nw(const View &sc, V o, V d, float time, uint64_t seg_key, float &best_t,
                                                 int &best_face, NwCount *cnt) {
   const float4 *nlo = LDS_NODES ? nw_nodes_lds : sc.nlo;
@@ -428,6 +555,7 @@ __device__ __forceinline__ int32_t hit_world_nw(const View &sc, V o, V d, float 
   best_face = -1;
   uint32_t med_hit = 0;
   const V invw = mk(drcp(d.x), drcp(d.y), drcp(d.z));  // hit_object's planes
+  const float2 trw = tri_world<TRI>(d);
   for (int32_t m = 0; m < sc.nmed; ++m) {
     const Obj ob = sc.med[m];
     const int32_t id = sc.med_id[m];
@@ -476,7 +604,7 @@ __device__ __forceinline__ int32_t hit_world_nw(const View &sc, V o, V d, float 
         const int32_t id = oids[k];
         float t;
         int face = -1;
-        if (hit_object(sc, ob, o, d, invw, time, t, face) && (t < best_t || (t == best_t && id < best_id))) {
+        if (hit_object<false, TRI>(sc, ob, o, d, invw, trw, time, t, face) && (t < best_t || (t == best_t && id < best_id))) {
           best_t = t;
           best = k;
           best_id = id;
@@ -508,7 +636,7 @@ __host__ __device__ constexpr size_t nw_grid_lds_bytes(int32_t nobj, int32_t nce
 // its coordinate scale), so inside a cell that lists it; an object listed in
 // several cells gives the same t each time.  The objects' boxes cover the
 // whole shutter (moving spheres) and the composed transform (instances).
-template <bool S = false>
+template <bool S = false, bool TRI = false>
 __device__ __forceinline__ int32_t hit_world_nw_grid(const View &sc, V o, V d, float time, uint64_t seg_key,
                                                      float &best_t, int &best_face, NwCount *cnt) {
   const DevObj *objs = reinterpret_cast<const DevObj *>(nw_nodes_lds);
@@ -523,8 +651,10 @@ __device__ __forceinline__ int32_t hit_world_nw_grid(const View &sc, V o, V d, f
   best_face = -1;
   uint32_t med_hit = 0;
   V invw = mk(0.f, 0.f, 0.f);
+  float2 trw = make_float2(0.f, 0.f);
   if constexpr (!S) {
     invw = mk(drcp(d.x), drcp(d.y), drcp(d.z));  // hit_object's planes
+    trw = tri_world<TRI>(d);
     for (int32_t m = 0; m < sc.nmed; ++m) {
       const Obj ob = sc.med[m];
       const int32_t id = sc.med_id[m];
@@ -553,7 +683,7 @@ __device__ __forceinline__ int32_t hit_world_nw_grid(const View &sc, V o, V d, f
     const int32_t id = oids[k];
     float t;
     int face = -1;
-    if (hit_object<S>(sc, ob, o, d, invw, time, t, face) && (t < best_t || (t == best_t && id < best_id))) {
+    if (hit_object<S, TRI>(sc, ob, o, d, invw, trw, time, t, face) && (t < best_t || (t == best_t && id < best_id))) {
       best_t = t;
       best = k;
       best_id = id;
@@ -725,7 +855,7 @@ __device__ __forceinline__ Rec make_rec_medium(const View &sc, const Obj &ob, V 
   r.n = mk(1.0f, 0.0f, 0.0f);
   return r;
 }
-template <bool S = false>
+template <bool S = false, bool TRI = false>
 __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, V dw, float time, float t, int face) {
   Rec r;
   r.mat = ob.mat;
@@ -754,6 +884,19 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
     const float inv_r = drcp(ob.g0[3]);
     n = mk(inv_r * (p.x - c.x), inv_r * (p.y - c.y), inv_r * (p.z - c.z));
     if (need_uv) sphere_uv(n, r.u, r.v);
+  } else if (TRI && okind == kTriangle) {
+    V v0, v1, v2;
+    tri_vertices(ob, v0, v1, v2);
+    const V e1 = sub3(v1, v0), e2 = sub3(v2, v0);
+    const V c = mk(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+    const float inv_len = drcp(dsqrt(dot3(c, c)));
+    n = mk(c.x * inv_len, c.y * inv_len, c.z * inv_len);
+    if (need_uv) {
+      float U, Vv, W, det, T;
+      (void)tri_edges(o, tri_axes(d), tri_ray(d), v0, v1, v2, U, Vv, W, det, T);
+      r.u = Vv / det;
+      r.v = W / det;
+    }
   } else {
     int kind = okind;
     float a0, a1, b0, b1;

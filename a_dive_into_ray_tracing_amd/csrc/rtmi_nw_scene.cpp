@@ -5,10 +5,13 @@
 // curand XORWOW restatement they draw from.  No device code.
 #include <algorithm>
 #include <cmath>
+#include <cerrno>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -188,6 +191,12 @@ Bounds local_bounds(const SNode &n, int32_t kind) {
       for (int a = 0; a < 3; ++a) {
         b.lo[a] = std::min(g[a], g[4 + a]);
         b.hi[a] = std::max(g[a], g[4 + a]);
+      }
+      break;
+    case kTriangle:  // nine consecutive values: v0, v1, v2
+      for (int a = 0; a < 3; ++a) {
+        b.lo[a] = std::min(g[a], std::min(g[3 + a], g[6 + a]));
+        b.hi[a] = std::max(g[a], std::max(g[3 + a], g[6 + a]));
       }
       break;
   }
@@ -526,6 +535,16 @@ void build_obj_grid(const std::vector<Bounds> &bounds, const std::vector<double>
   out.grid_ok = true;
 }
 
+// A triangle whose float vertices are collinear: cross(v1 - v0, v2 - v0),
+// evaluated in double from the stored floats, is the zero vector.  It has no
+// normal, and the renderer never hits it.
+bool collinear_triangle(const Obj &o) {
+  if (o.kind != kTriangle) return false;
+  const double v0[3] = {o.g0[0], o.g0[1], o.g0[2]}, v1[3] = {o.g0[3], o.g1[0], o.g1[1]}, v2[3] = {o.g1[2], o.g1[3], o.g2[0]};
+  const double e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+  return e1[1] * e2[2] - e1[2] * e2[1] == 0.0 && e1[2] * e2[0] - e1[0] * e2[2] == 0.0 && e1[0] * e2[1] - e1[1] * e2[0] == 0.0;
+}
+
 }  // namespace
 
 namespace rtmi {
@@ -546,6 +565,9 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       med_index[k] = int32_t(out.med.size());
       out.med.push_back(s->flat_obj[k]);
       out.med_id.push_back(k);
+    } else if (collinear_triangle(s->flat_obj[k])) {
+      // never hit (rt_nw_triangle): it keeps its insertion index and joins
+      // neither the BVH nor the grid
     } else {
       ids.push_back(k);
     }
@@ -559,12 +581,13 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       scale = std::max(scale, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
     }
   }
-  // relative test costs: a box is six rectangle tests, an instance adds a
-  // ray transform
+  // relative test costs: a box is six rectangle tests, a triangle ~47 flop
+  // against a sphere's ~30 with its square root, an instance adds a ray
+  // transform
   std::vector<double> cost(n_all, 1.0);
   for (int k = 0; k < n_all; ++k) {
     const Obj &o = s->flat_obj[k];
-    cost[k] = (o.kind == kBox ? 3.0 : o.kind == kMovingSphere ? 1.2 : 1.0) + (o.inst >= 0 ? 0.3 : 0.0);
+    cost[k] = (o.kind == kBox ? 3.0 : o.kind == kMovingSphere ? 1.2 : o.kind == kTriangle ? 1.5 : 1.0) + (o.inst >= 0 ? 0.3 : 0.0);
   }
   // box margins (the RTIOW BVH's argument): 1e-3 of the
   // object's own coordinate scale — ~100x the float error of its hit test —
@@ -768,9 +791,279 @@ RTMI_EXPORT int rt_nw_box(rt_nw_scene *s, const double p0[3], const double p1[3]
   return add_node(s, n);
 }
 
+// ---------------------------------------------------------------------------
+// triangles, meshes and the Wavefront OBJ reader
+// ---------------------------------------------------------------------------
+namespace {
+
+// One triangle node from three double vertices; the winding is final here.
+// Rejected: a coordinate that is not finite as a float, or two vertices equal
+// as floats (what the device tests).  Collinear vertices are allowed: such a
+// triangle is never hit (build_device_scene leaves it out of the BVH and the
+// grid, collinear_triangle).
+int add_triangle(rt_nw_scene *s, const double *v0, const double *v1, const double *v2, int32_t mat, const char *who) {
+  const double *v[3] = {v0, v1, v2};
+  float f[3][3];
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 3; ++a) {
+      f[k][a] = float(v[k][a]);
+      if (!std::isfinite(f[k][a])) return set_error(RT_EINVAL, "%s: vertex coordinate not finite", who);
+    }
+  for (int k = 0; k < 3; ++k) {
+    const int j = (k + 1) % 3;
+    if (f[k][0] == f[j][0] && f[k][1] == f[j][1] && f[k][2] == f[j][2])
+      return set_error(RT_EINVAL, "%s: degenerate triangle (two equal vertices)", who);
+  }
+  SNode n;
+  n.kind = kTriangle;
+  n.mat = mat;
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 3; ++a) n.g[3 * k + a] = v[k][a];
+  return add_node(s, n);
+}
+
+// The shared builder of rt_nw_mesh and rt_nw_load_obj.  nidx entries may be
+// -1 only when allow_missing (an OBJ face without normals keeps its winding).
+// line_of (may be null): the file line of each triangle, for error messages.
+int add_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri, int32_t n_tris,
+             const double *normals, int32_t n_normals, const int32_t *nidx, bool allow_missing, int32_t mat,
+             const int32_t *line_of, const char *who) {
+  SNode grp;
+  grp.type = kGroup;
+  grp.kids.reserve(size_t(n_tris));
+  std::string where;
+  for (int32_t t = 0; t < n_tris; ++t) {
+    if (line_of) where = std::string(who) + ": line " + std::to_string(line_of[t]);
+    else where = std::string(who) + ": triangle " + std::to_string(t);
+    const int32_t *ix = tri + 3 * size_t(t);
+    for (int c = 0; c < 3; ++c)
+      if (ix[c] < 0 || ix[c] >= n_verts) return set_error(RT_EINVAL, "%s: vertex index %d out of range", where.c_str(), ix[c]);
+    const double *v0 = verts + 3 * size_t(ix[0]), *v1 = verts + 3 * size_t(ix[1]), *v2 = verts + 3 * size_t(ix[2]);
+    if (normals) {
+      const int32_t *nx = nidx ? nidx + 3 * size_t(t) : ix;
+      double ns[3] = {0, 0, 0};
+      bool have = true;
+      for (int c = 0; c < 3; ++c) {
+        if (nx[c] == -1 && allow_missing) { have = false; continue; }
+        if (nx[c] < 0 || nx[c] >= n_normals) return set_error(RT_EINVAL, "%s: normal index %d out of range", where.c_str(), nx[c]);
+        for (int a = 0; a < 3; ++a) ns[a] += normals[3 * size_t(nx[c]) + a];
+      }
+      if (have) {  // front = the side of the normals' sum (the OBJ convention)
+        const double e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+        const double fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        if (fn[0] * ns[0] + fn[1] * ns[1] + fn[2] * ns[2] < 0) std::swap(v1, v2);
+      }
+    }
+    const int id = add_triangle(s, v0, v1, v2, mat, where.c_str());
+    if (id < 0) return id;
+    grp.kids.push_back(id);
+  }
+  return add_node(s, grp);
+}
+
+}  // namespace
+
+RTMI_EXPORT int rt_nw_triangle(rt_nw_scene *s, const double v0[3], const double v1[3], const double v2[3], int32_t mat) {
+  if (!s || !v0 || !v1 || !v2 || !valid_mat(s, mat)) return set_error(RT_EINVAL, "rt_nw_triangle: bad argument");
+  return add_triangle(s, v0, v1, v2, mat, "rt_nw_triangle");
+}
+
+RTMI_EXPORT int rt_nw_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri_idx, int32_t n_tris,
+                           const double *normals, int32_t n_normals, const int32_t *normal_idx, int32_t mat) {
+  if (!s || !verts || !tri_idx || n_verts < 1 || n_tris < 1 || !valid_mat(s, mat) || (normals && n_normals < 1) ||
+      (!normals && normal_idx))
+    return set_error(RT_EINVAL, "rt_nw_mesh: bad argument");
+  return add_mesh(s, verts, n_verts, tri_idx, n_tris, normals, n_normals, normal_idx, false, mat, nullptr, "rt_nw_mesh");
+}
+
+// Wavefront OBJ: v, vn and f (a, a/t, a//n, a/t/n; negative indices count
+// back from the latest vertex / normal; polygons fan-triangulated in the
+// file's winding).  Every other statement is ignored.
+namespace {
+struct ObjFile {
+  std::vector<double> verts, normals;
+  std::vector<int32_t> tri, nidx, line_of;  // nidx: -1 for a corner without a normal
+};
+int parse_obj(const char *path, ObjFile &out) {
+  FILE *f = std::fopen(path, "rb");
+  if (!f) return set_error(RT_EIO, "rt_nw_load_obj: cannot open %s", path);
+  std::vector<double> &verts = out.verts, &normals = out.normals;
+  std::vector<int32_t> &tri = out.tri, &nidx = out.nidx, &line_of = out.line_of;
+  std::string line;
+  int lineno = 0, rc = RT_OK;
+  // one number of a v / vn statement: the whole token must parse
+  auto number = [](const char *&p, double &out) {
+    while (*p == ' ' || *p == '\t') ++p;
+    if (!*p) return false;
+    char *end = nullptr;
+    errno = 0;
+    out = std::strtod(p, &end);
+    if (end == p || (*end && *end != ' ' && *end != '\t')) return false;
+    p = end;
+    return true;
+  };
+  // one integer of a face corner; stops at '/', blank or the end
+  auto integer = [](const char *&p, long &out) {
+    char *end = nullptr;
+    errno = 0;
+    out = std::strtol(p, &end, 10);
+    if (end == p || errno == ERANGE) return false;
+    p = end;
+    return true;
+  };
+  for (bool eof = false; !eof && rc == RT_OK;) {
+    line.clear();
+    int c;
+    while ((c = std::fgetc(f)) != EOF && c != '\n') line.push_back(char(c));
+    if (c == EOF) {
+      eof = true;
+      if (line.empty()) break;
+    }
+    ++lineno;
+    if (line.find('\0') != std::string::npos) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: NUL byte", path, lineno); break; }
+    if (const size_t hash = line.find('#'); hash != std::string::npos) line.erase(hash);  // comment
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+    const char *p = line.c_str();
+    while (*p == ' ' || *p == '\t') ++p;
+    const bool is_v = p[0] == 'v' && (p[1] == ' ' || p[1] == '\t');
+    const bool is_vn = p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t');
+    const bool is_f = p[0] == 'f' && (p[1] == ' ' || p[1] == '\t');
+    if (is_v || is_vn) {
+      p += is_v ? 1 : 2;
+      double x[3];
+      for (int a = 0; a < 3 && rc == RT_OK; ++a)
+        if (!number(p, x[a])) rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed number", path, lineno);
+      if (rc) break;
+      if (is_v) {  // an optional w (and vertex colours) may follow: numbers still
+        double extra;
+        while (*p)
+          if (!number(p, extra)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed number", path, lineno); break; }
+        if (rc) break;
+      }
+      std::vector<double> &dst = is_v ? verts : normals;
+      dst.insert(dst.end(), x, x + 3);
+    } else if (is_f) {
+      p += 1;
+      std::vector<int32_t> cv, cn;
+      const long nv = long(verts.size() / 3), nn = long(normals.size() / 3);
+      for (;;) {
+        while (*p == ' ' || *p == '\t') ++p;
+        if (!*p) break;
+        long iv = 0, in = 0, it = 0;
+        bool has_n = false;
+        if (!integer(p, iv)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+        if (*p == '/') {
+          ++p;
+          if (*p != '/' && !integer(p, it)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+          if (*p == '/') {
+            ++p;
+            if (!integer(p, in)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+            has_n = true;
+          }
+        }
+        if (*p && *p != ' ' && *p != '\t') { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+        const long av = iv < 0 ? nv + iv : iv - 1, an = !has_n ? -1 : in < 0 ? nn + in : in - 1;
+        if (iv == 0 || av < 0 || av >= nv) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: vertex index %ld out of range", path, lineno, iv); break; }
+        if (has_n && (in == 0 || an < 0 || an >= nn)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: normal index %ld out of range", path, lineno, in); break; }
+        cv.push_back(int32_t(av));
+        cn.push_back(int32_t(an));
+      }
+      if (rc) break;
+      if (cv.size() < 3) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: face with fewer than three corners", path, lineno); break; }
+      for (size_t k = 1; k + 1 < cv.size(); ++k) {  // fan about the first corner
+        const size_t c3[3] = {0, k, k + 1};
+        for (size_t q : c3) {
+          tri.push_back(cv[q]);
+          nidx.push_back(cn[q]);
+        }
+        line_of.push_back(lineno);
+      }
+      if (tri.size() / 3 >= (size_t(1) << 27)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: too many triangles", path); break; }
+    }
+    // vt, o, g, s, usemtl, mtllib, comments, blank lines, anything else: ignored
+  }
+  const bool io_error = std::ferror(f) != 0;
+  std::fclose(f);
+  if (rc) return rc;
+  if (io_error) return set_error(RT_EIO, "rt_nw_load_obj: read error in %s", path);
+  if (tri.empty()) return set_error(RT_EINVAL, "rt_nw_load_obj: %s: no faces", path);
+  return RT_OK;
+}
+int add_obj_mesh(rt_nw_scene *s, const char *path, const ObjFile &o, int32_t mat, int32_t *n_tris) {
+  const int32_t nt = int32_t(o.tri.size() / 3);
+  const std::string who = std::string("rt_nw_load_obj: ") + path;
+  const bool nrm = !o.normals.empty();
+  const int id = add_mesh(s, o.verts.data(), int32_t(o.verts.size() / 3), o.tri.data(), nt, nrm ? o.normals.data() : nullptr,
+                          int32_t(o.normals.size() / 3), nrm ? o.nidx.data() : nullptr, true, mat, o.line_of.data(), who.c_str());
+  if (id >= 0 && n_tris) *n_tris = nt;
+  return id;
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, int32_t *n_tris) {
+  if (!s || !path || !valid_mat(s, mat)) return set_error(RT_EINVAL, "rt_nw_load_obj: bad argument");
+  ObjFile o;
+  if (int rc = parse_obj(path, o)) return rc;
+  return add_obj_mesh(s, path, o, mat, n_tris);
+}
+
+// The scene of `rtmi_nw_render --obj`: the file's mesh scaled (uniformly) and
+// centred into the box [-1, 1] x [0, 2] x [-1, 1] — its largest extent 2 units,
+// standing on y = 0 — on a checker ground (a sphere of radius 1000 below it),
+// one 3 x 3 xz_rect light of emission 6 at y = 5 and the background (0.05,
+// 0.07, 0.12).  Camera: from (3.2, 2.4, 4.8) at the box centre (0, 1, 0),
+// vfov 30, no aperture.
+RTMI_EXPORT int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, double aspect, rt_nw_camera *cam,
+                                      int32_t *n_tris) {
+  if (!s || !path || !cam || !(aspect > 0)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
+  if (mat_kind != RT_NW_LAMBERTIAN && mat_kind != RT_NW_METAL && mat_kind != RT_NW_DIELECTRIC)
+    return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: material must be lambertian, metal or dielectric");
+  ObjFile o;
+  if (int rc = parse_obj(path, o)) return rc;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int32_t ix : o.tri)  // the vertices the faces use
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(lo[a], o.verts[3 * size_t(ix) + a]);
+      hi[a] = std::max(hi[a], o.verts[3 * size_t(ix) + a]);
+    }
+  const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+  if (!(ext > 0) || !std::isfinite(ext)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: %s: mesh without extent", path);
+  const double k = 2.0 / ext, c[3] = {0.5 * (lo[0] + hi[0]), lo[1], 0.5 * (lo[2] + hi[2])};
+  for (size_t i = 0; i < o.verts.size(); ++i) o.verts[i] = (o.verts[i] - c[i % 3]) * k;
+  int rc = RT_OK;
+  auto chk = [&](int v) {
+    if (v < 0 && rc == RT_OK) rc = v;
+    return v;
+  };
+  const int mat = mat_kind == RT_NW_LAMBERTIAN ? chk(rt_nw_mat_lambertian(s, chk(rt_nw_tex_solid(s, 0.7, 0.35, 0.2))))
+                  : mat_kind == RT_NW_METAL    ? chk(rt_nw_mat_metal(s, chk(rt_nw_tex_solid(s, 0.8, 0.8, 0.85)), 0.05))
+                                               : chk(rt_nw_mat_dielectric(s, 1.5));
+  if (rc) return rc;
+  const int mesh = chk(add_obj_mesh(s, path, o, mat, n_tris));
+  const double gc[3] = {0, -1000, 0};
+  const int ground = chk(rt_nw_sphere(s, gc, 1000, chk(rt_nw_mat_lambertian(s, chk(rt_nw_tex_checker(
+                                                      s, chk(rt_nw_tex_solid(s, 0.2, 0.3, 0.1)), chk(rt_nw_tex_solid(s, 0.9, 0.9, 0.9))))))));
+  const int light = chk(rt_nw_rect(s, RT_NW_XZ, -1.5, 1.5, -1.5, 1.5, 5.0, chk(rt_nw_mat_diffuse_light(s, chk(rt_nw_tex_solid(s, 6, 6, 6))))));
+  if (rc) return rc;
+  chk(rt_nw_world_add(s, ground));
+  chk(rt_nw_world_add(s, mesh));
+  chk(rt_nw_world_add(s, light));
+  chk(rt_nw_set_background(s, 0.05, 0.07, 0.12));
+  if (rc) return rc;
+  const double from[3] = {3.2, 2.4, 4.8}, at[3] = {0, 1, 0}, vup[3] = {0, 1, 0};
+  const double dist = std::sqrt(3.2 * 3.2 + 1.4 * 1.4 + 4.8 * 4.8);
+  return rt_nw_camera_init(cam, from, at, vup, 30.0, aspect, 0.0, dist, 0.0, 1.0);
+}
+
 RTMI_EXPORT int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex) {
   if (!s || !valid_node(s, boundary) || !valid_tex(s, tex) || !(density > 0))
     return set_error(RT_EINVAL, "rt_nw_constant_medium: bad argument");
+  {  // a triangle (under any translate / rotate_y chain) bounds no volume
+    int32_t b = boundary;
+    while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate)) b = s->nodes[b].child;
+    if (valid_node(s, b) && s->nodes[b].type == kPrim && s->nodes[b].kind == kTriangle)
+      return set_error(RT_EUNSUPPORTED, "rt_nw_constant_medium: a triangle cannot be a medium's boundary");
+  }
   const int m = rt_nw_mat_isotropic(s, tex);  // phase_function = new isotropic(a) constant_medium.h:12-17
   if (m < 0) return m;
   SNode n;

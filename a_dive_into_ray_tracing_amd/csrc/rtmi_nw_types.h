@@ -18,6 +18,8 @@ enum ObjKind : int32_t {
   kBox = 5,           // box.h               g0 = {p0, 0}, g1 = {p1, 0}
   kMedium = 6,        // constant_medium.h   boundary geometry as its kind (aux & 255), g2.w = -1/density,
                       //                     aux >> 8 = scattering-distance samples
+  kTriangle = 7,      // triangle (two-sided, watertight): the vertices as nine floats,
+                      //                     g0 = {v0, v1.x}, g1 = {v1.y, v1.z, v2.x, v2.y}, g2.x = v2.z
 };
 
 // material kinds = RT_NW_* (rtmi_nw.h)
@@ -33,12 +35,12 @@ struct Obj {  // 64 B
 constexpr int kMaxMedia = 32;
 // The device's record of a non-medium object (48 B: three float4 loads, 25%
 // less LDS than Obj): media live in their own list, so only the moving
-// sphere's time1 remains of g2.
+// sphere's time1 — or a triangle's ninth float, v2.z — remains of g2.
 struct DevObj {
   float g0[4], g1[4];
   int32_t ka;  // kind | aux << 8 (one 32-bit field: no sub-dword loads)
   int32_t mat;
-  float t1;  // moving sphere: time1 (Obj g2[0])
+  float t1;  // moving sphere: time1; triangle: v2.z (Obj g2[0])
   int32_t inst;
 };
 static_assert(sizeof(DevObj) == 48, "DevObj layout");

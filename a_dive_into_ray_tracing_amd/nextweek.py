@@ -20,7 +20,7 @@ import numpy as np
 
 from ._abi import RtNwCamera, RtNwFlat, check, load
 
-__all__ = ["Scene", "NwRenderer", "camera", "preset", "xorwow_uniforms", "load_image", "SCENES"]
+__all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "SCENES"]
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -109,6 +109,32 @@ class Scene:
     def box(self, p0, p1, mat):
         return _id(load().rt_nw_box(self._h, _v3(p0), _v3(p1), mat), "rt_nw_box")
 
+    def triangle(self, v0, v1, v2, mat):
+        """A two-sided, watertight triangle; counter-clockwise is front."""
+        return _id(load().rt_nw_triangle(self._h, _v3(v0), _v3(v1), _v3(v2), mat), "rt_nw_triangle")
+
+    def mesh(self, verts, faces, normals=None, mat=None, normal_faces=None):
+        """Triangles `faces` (n x 3 vertex indices) over `verts` (m x 3) as
+        one handle; `normals` (k x 3), indexed by `normal_faces` (n x 3) or,
+        without it, by the vertex indices, fix the winding (rt_nw_mesh)."""
+        if mat is None:
+            raise TypeError("Scene.mesh: mat is required")
+        v = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+        nf = None if normal_faces is None else np.ascontiguousarray(normal_faces, np.int32).reshape(-1, 3)
+        if nf is not None and len(nf) != len(f):
+            raise ValueError("Scene.mesh: normal_faces must have one row per face")
+        return _id(load().rt_nw_mesh(self._h, v.ctypes.data_as(_dp), len(v), f.ctypes.data_as(_ip), len(f),
+                                     None if nrm is None else nrm.ctypes.data_as(_dp), 0 if nrm is None else len(nrm),
+                                     None if nf is None else nf.ctypes.data_as(_ip), mat), "rt_nw_mesh")
+
+    def load_obj(self, path, mat):
+        """A Wavefront OBJ file as one mesh (rt_nw_load_obj): (handle, triangle count)."""
+        n = C.c_int32()
+        h = _id(load().rt_nw_load_obj(self._h, str(path).encode(), mat, C.byref(n)), "rt_nw_load_obj")
+        return h, n.value
+
     def constant_medium(self, boundary, density, tex):
         return _id(load().rt_nw_constant_medium(self._h, boundary, float(density), tex), "rt_nw_constant_medium")
 
@@ -182,6 +208,18 @@ def preset(which, image=None, aspect=1.0, rtl=False):
     check(load().rt_nw_scene_preset(s._h, int(w), ptr, iw, ih, float(aspect), 1 if rtl else 0, C.byref(cam)),
           "rt_nw_scene_preset")
     return s, cam
+
+
+def obj_stage(path, mat="lambertian", aspect=1.0):
+    """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera
+    (rt_nw_scene_obj_stage): (scene, camera, triangle count)."""
+    kind = {"lambertian": 0, "metal": 1, "glass": 2, "dielectric": 2}[mat]
+    s = Scene()
+    cam = RtNwCamera()
+    n = C.c_int32()
+    check(load().rt_nw_scene_obj_stage(s._h, str(path).encode(), kind, float(aspect), C.byref(cam), C.byref(n)),
+          "rt_nw_scene_obj_stage")
+    return s, cam, n.value
 
 
 def xorwow_uniforms(n, seed=1984):
@@ -274,6 +312,12 @@ class NwRenderer:
         v = (C.c_int32 * 4)()
         check(load().rt_nw_ctx_last_kernel(self._h, v), "rt_nw_ctx_last_kernel")
         return dict(zip(("persistent", "grid", "spheres_only", "chunk"), list(v)))
+
+    def last_staging(self):
+        """Diagnostic: what the last render walked from LDS (rt_nw_ctx_last_staging)."""
+        v = (C.c_int32 * 2)()
+        check(load().rt_nw_ctx_last_staging(self._h, v), "rt_nw_ctx_last_staging")
+        return {"nodes_lds": bool(v[0]), "objects_lds": bool(v[1])}
 
     def close(self):
         if self._h:

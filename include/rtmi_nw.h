@@ -73,8 +73,44 @@ int rt_nw_moving_sphere(rt_nw_scene *s, const double center0[3], const double ce
  * order (xy: x,y; xz: x,z; yz: y,z), k the plane coordinate. */
 int rt_nw_rect(rt_nw_scene *s, int32_t plane, double a0, double a1, double b0, double b1, double k, int32_t mat);
 int rt_nw_box(rt_nw_scene *s, const double p0[3], const double p1[3], int32_t mat);
+/* A triangle (the reference's triangles/ chapter, triangle.h), two-sided and
+ * watertight (Woop, Benthin, Wald 2013): counter-clockwise
+ * vertices face front — the side a dielectric is entered from — and shading
+ * is flat.  RT_EINVAL: a coordinate not finite as a float, or two vertices
+ * equal as floats (three collinear ones are accepted and never hit: the
+ * device scene leaves such a triangle out). */
+int rt_nw_triangle(rt_nw_scene *s, const double v0[3], const double v1[3], const double v2[3], int32_t mat);
+/* n_tris triangles over n_verts vertices (xyz each; tri_idx: three vertex
+ * indices per triangle); one handle for the set, used like rt_nw_group's.
+ * normals (n_normals xyz, may be NULL) fix the winding: a triangle whose
+ * cross(v1 - v0, v2 - v0) points away from the sum of its corners' normals
+ * has v1 and v2 exchanged.  normal_idx (three per triangle) may be NULL:
+ * the corners then take the normals of their vertex indices.  Any index out
+ * of range or negative: RT_EINVAL. */
+int rt_nw_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri_idx, int32_t n_tris,
+               const double *normals, int32_t n_normals, const int32_t *normal_idx, int32_t mat);
+/* A Wavefront OBJ file as one mesh of material `mat`; *n_tris (may be NULL)
+ * its triangle count.  Read: v, vn, and f with corners a, a/t, a//n or
+ * a/t/n, negative indices counting back from the latest statement; polygons
+ * are fan-triangulated in the file's winding, and faces with normals get
+ * rt_nw_mesh's winding fix.  Ignored: vt, o, g, s, usemtl, mtllib (no file
+ * but `path` is opened), '#' comments, blank lines, CR LF endings.
+ * RT_EINVAL with the line number in rt_last_error(): a malformed number or
+ * index, an index out of range, a face with fewer than three corners, a
+ * degenerate triangle; RT_EIO: the file cannot be opened or read. */
+int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, int32_t *n_tris);
+/* The scene of `rtmi_nw_render --obj` into an empty scene: the file's mesh
+ * scaled uniformly and centred into [-1, 1] x [0, 2] x [-1, 1] (largest extent
+ * 2 units, standing on y = 0) with material mat_kind (RT_NW_LAMBERTIAN,
+ * _METAL or _DIELECTRIC), on a checker ground, under one 3 x 3 xz_rect light
+ * (emission 6) at y = 5, background (0.05, 0.07, 0.12); writes the camera:
+ * from (3.2, 2.4, 4.8) at the box centre (0, 1, 0), vfov 30, no aperture.
+ * Errors as rt_nw_load_obj. */
+int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, double aspect, rt_nw_camera *cam,
+                          int32_t *n_tris);
 /* constant_medium(boundary, density, tex) constant_medium.h: boundary is a
- * sphere, moving sphere or box object, optionally under translate/rotate_y. */
+ * sphere, moving sphere or box object, optionally under translate/rotate_y
+ * (a rectangle, a triangle or a set of objects: RT_EUNSUPPORTED). */
 int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex);
 /* Scattering-distance samples of a medium per ray segment (1..8, default 1):
  * each draws -log(u)/density anew and the last one that lands inside the
@@ -114,7 +150,9 @@ int rt_nw_xorwow_uniforms(uint64_t seed, int32_t n, float *out);
  *   obj  : n_obj * 16 floats: g0[4] g1[4] g2[4] then kind, mat, inst, aux as
  *          int32 bit patterns (layout: DESIGN.md §9; aux: medium -> boundary
  *          kind | samples << 8, other -> insertion index of the medium whose
- *          boundary it is + 1, or 0)
+ *          boundary it is + 1, or 0).  A triangle (kind 7) stores its
+ *          vertices as nine floats: g0 = {v0.xyz, v1.x}, g1 = {v1.y, v1.z,
+ *          v2.x, v2.y}, g2[0] = v2.z, in the winding the builder settled.
  *   inst : n_inst * 8 floats: cos, sin, off.x, off.y, off.z, flags(int bits), 0, 0
  *   mat  : n_mat * 4: kind(int bits), tex(int bits), fuzz, ir
  *   tex  : n_tex * 8: kind, a, b, 0 (int bits), r, g, b, scale
@@ -187,6 +225,9 @@ int rt_nw_ctx_last_segments(rt_nw_ctx *ctx, uint64_t *segments);
  * media, solid / checker textures: the other kinds' code compiled out),
  * samples per work item}.  Same image for every choice. */
 int rt_nw_ctx_last_kernel(rt_nw_ctx *ctx, int32_t *out4);
+/* Diagnostic: what the last render's kernel walked from LDS, {BVH nodes,
+ * object records} (1 / 0; the uniform grid stages the objects, no nodes). */
+int rt_nw_ctx_last_staging(rt_nw_ctx *ctx, int32_t out2[2]);
 /* Analysis builds only (-DRTMI_NW_PHASES=1): wave-level cycles of the loop
  * passes since the last call — closest hit, hit record + texture + scatter,
  * accumulation + regeneration, whole items; RT_EUNSUPPORTED otherwise. */
