@@ -132,6 +132,13 @@ SIGNATURES = {
     "rt_nw_mesh": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, C.c_int32, _dp, C.c_int32, _ip, C.c_int32]),
     "rt_nw_load_obj": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _ip]),
     "rt_nw_scene_obj_stage": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
+    "rt_nw_mesh_attr": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip,
+                                  C.c_uint32, C.c_int32]),
+    "rt_nw_load_obj_attr": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, _ip]),
+    "rt_nw_scene_obj_stage_attr": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
+                                             C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
+    "rt_nw_scene_flat_attr": (C.c_int, [C.c_void_p, _ip, C.POINTER(_fp), C.POINTER(_ip)]),
+    "rt_nw_debug_records": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _fp, _ip]),
     "rt_nw_constant_medium": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     "rt_nw_medium_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rt_nw_group": (C.c_int, [C.c_void_p, _ip, C.c_int32]),

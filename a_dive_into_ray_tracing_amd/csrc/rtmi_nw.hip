@@ -173,7 +173,7 @@ __device__ __forceinline__ void stage_scene(const View &sc) {
 // One work item = (8x8 tile, <= chunk samples) on one wave: lanes pull
 // (pixel, sample) jobs from the item's queue and regenerate paths as theirs
 // end; sums in the wave's LDS accumulator, then one global add per pixel.
-template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false, bool TRI = false>
+template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
 __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item, int lane,
                                          unsigned long long (&acc)[3][64], unsigned long long *__restrict__ accum,
                                          float *__restrict__ out, unsigned &nseg, const float *cl) {
@@ -262,7 +262,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
         col = mk(T.x * sc.bg[0], T.y * sc.bg[1], T.z * sc.bg[2]);
         done = true;
       } else {
-        const Rec rec = S || k < sc.nobj ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face)
+        const Rec rec = S || k < sc.nobj ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face, attr_view_of(sc), k)
                                          : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
         const Mat m = sc.mat[rec.mat];
         V at, nd;
@@ -338,8 +338,9 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
   if (lane == 0) atomicAdd(segments, (unsigned long long)nseg);  // the wave's world.hit calls (wave-uniform)
 }
 
-// TRI (last parameter of both kernels): the scene holds triangles (hit_object)
-template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool TRI = false>
+// TRI (last parameter of both kernels): the scene holds no triangle (0), triangles (1), triangles with
+// attribute records (2; hit_object, make_rec)
+template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, int TRI = 0>
 __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, unsigned long long *__restrict__ accum,
                                                              float *__restrict__ out,
                                                              unsigned long long *__restrict__ segments) {
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
 #ifndef RTMI_NW_PERSIST_GRID_PER_EU
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
-template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, bool TRI = false>
+template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
 __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : RTMI_NW_PERSIST_PER_EU)) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
@@ -386,8 +387,10 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
 // Debug (parity investigations): the segments of ONE camera sample (pixel
 // i, j, sample s): per segment o.xyz, d.xyz, t, winner insertion index (as
 // float bits) — the oracle's or_nw_trace records the same.
-__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
+// has_attr: the scene has triangle attribute records (attr_view_of).
+__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const AttrView av = has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr};
   Xoro rng;
   rng.init(a.seed, uint64_t(j) * uint64_t(a.W) + uint64_t(i), uint32_t(s));
   float ju, jv;
@@ -403,14 +406,14 @@ __global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, i
     const uint64_t seg_key = sc.has_media ? rng.next() : 0ull;
     float t;
     int face;
-    const int32_t k = hit_world_nw<false, false, true>(sc, o, d, time, seg_key, t, face, &tcnt);
+    const int32_t k = hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
     r[7] = __int_as_float(k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj]);
     r[8] = r[9] = r[10] = 0.f;
     r[11] = __int_as_float(face);
     if (k < 0) break;
-    const Rec rc = k < sc.nobj ? make_rec<false, true>(sc, sc.obj[k], o, d, time, t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
+    const Rec rc = k < sc.nobj ? make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
     V at, nd;
@@ -443,11 +446,51 @@ __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *_
   NwCount cnt{0, 0, 0, 0};
   float t;
   int face;
-  const int32_t k = GRID ? hit_world_nw_grid<false, true>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
-                         : hit_world_nw<false, false, true>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
+  const int32_t k = GRID ? hit_world_nw_grid<false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
+                         : hit_world_nw<false, false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
   out_id[i] = k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_face[i] = face;
+}
+
+// The hit record of n given rays (validation: rt_nw_debug_records): the
+// closest hit as debug_hits_kernel resolves it, then the record a render makes
+// of it (make_rec with the attribute path, make_rec_medium).  Out per ray: the
+// winner's insertion index (-1: miss, everything else zero), t, {p.xyz, n.xyz,
+// u, v} and the material.
+template <bool GRID>
+__global__ __launch_bounds__(256) void debug_records_kernel(View sc, const float *__restrict__ rays,
+                                                            const unsigned long long *__restrict__ keys, int32_t n,
+                                                            int has_attr, int32_t *__restrict__ out_id,
+                                                            float *__restrict__ out_t, float *__restrict__ out_pnuv,
+                                                            int32_t *__restrict__ out_mat) {
+  stage_scene<false, false, GRID>(sc);  // (GRID: ends with the block barrier, before any thread leaves)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *r = rays + 8 * size_t(i);
+  const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
+  NwCount cnt{0, 0, 0, 0};
+  float t;
+  int face;
+  const int32_t k = GRID ? hit_world_nw_grid<false, 2>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
+                         : hit_world_nw<false, false, 2>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
+  float *q = out_pnuv + 8 * size_t(i);
+  if (k < 0) {
+    out_id[i] = -1;
+    out_t[i] = 0.0f;
+    out_mat[i] = 0;
+    for (int c = 0; c < 8; ++c) q[c] = 0.0f;
+    return;
+  }
+  const AttrView av = has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr};
+  const Rec rc = k < sc.nobj ? make_rec<false, 2>(sc, sc.obj[k], o, d, r[6], t, face, av, k)
+                             : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
+  out_id[i] = k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
+  out_t[i] = t;
+  out_mat[i] = rc.mat;
+  q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
+  q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
+  q[6] = rc.u; q[7] = rc.v;
 }
 
 }  // namespace nw
@@ -492,7 +535,8 @@ struct rt_nw_ctx {
   int32_t accel = RT_NW_ACCEL_AUTO;
   float bg[3] = {0.f, 0.f, 0.f};
   int32_t has_media = 0;
-  int32_t has_tri = 0;
+  int32_t has_tri = 0;  // the kernels' TRI: 0 no triangle, 1 triangles, 2 triangles with attribute records
+  int32_t nattr = 0;    // attribute records behind obj[nobj] (their locator behind obj_id[nobj]); 0: neither exists
   unsigned long long *accum = nullptr;
   size_t accum_cap = 0;
   float *scratch = nullptr;
@@ -672,7 +716,20 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
     split[i] = make_float4(nd.bmin[0], nd.bmin[1], nd.bmin[2], sk);
     split[ds.nodes.size() + i] = make_float4(nd.bmax[0], nd.bmax[1], nd.bmax[2], lf);
   }
-  std::vector<DevObj> dobj(ds.obj.size());
+  // attribute records: the locator holds one entry per object, -1 or a record of a triangle
+  const size_t nattr = ds.obj_attr.empty() ? 0 : ds.attr.size();
+  if (!ds.obj_attr.empty() && (ds.obj_attr.size() != ds.obj.size() || nattr == 0))
+    return set_error(RT_EINVAL, "rt_nw: attribute locator does not match the objects");
+  for (size_t i = 0; i < ds.obj_attr.size(); ++i)
+    if (ds.obj_attr[i] < -1 || ds.obj_attr[i] >= int32_t(nattr) || (ds.obj_attr[i] >= 0 && ds.obj[i].kind != kTriangle))
+      return set_error(RT_EINVAL, "rt_nw: attribute record index out of range");
+  // the records follow the objects in one allocation and the locator follows
+  // the insertion indices (rtmi_nw_path.h attr_view_of): 64 B records behind
+  // 48 B ones, so the tail is sized in DevObj units
+  std::vector<DevObj> dobj(ds.obj.size() + (nattr * sizeof(TriAttr) + sizeof(DevObj) - 1) / sizeof(DevObj));
+  if (nattr) std::memcpy(static_cast<void *>(dobj.data() + ds.obj.size()), ds.attr.data(), nattr * sizeof(TriAttr));
+  std::vector<int32_t> dobj_id = ds.obj_id;
+  if (nattr) dobj_id.insert(dobj_id.end(), ds.obj_attr.begin(), ds.obj_attr.end());
   for (size_t i = 0; i < ds.obj.size(); ++i) {
     const Obj &o = ds.obj[i];
     DevObj &q = dobj[i];
@@ -696,14 +753,14 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   Guard g(ctx->device);
   // the context's structures are replaced below: until that completes, no
   // render may use a mix of old counts and new buffers
-  ctx->nobj = ctx->nmed = ctx->nnodes = 0;
+  ctx->nobj = ctx->nmed = ctx->nnodes = ctx->nattr = 0;
   ctx->grid_ok = false;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   int rc;
   if ((rc = alloc_copy(&ctx->obj, dobj.data(), dobj.size())) ||
       (rc = alloc_copy(&ctx->med, ds.med.data(), ds.med.size())) ||
       (rc = alloc_copy(&ctx->med_id, ds.med_id.data(), ds.med_id.size())) ||
-      (rc = alloc_copy(&ctx->obj_id, ds.obj_id.data(), ds.obj_id.size())) ||
+      (rc = alloc_copy(&ctx->obj_id, dobj_id.data(), dobj_id.size())) ||
       (rc = alloc_copy(&ctx->inst, ds.inst.data(), ds.inst.size())) ||
       (rc = alloc_copy(&ctx->mat, ds.mat.data(), ds.mat.size())) ||
       (rc = alloc_copy(&ctx->tex, ds.tex.data(), ds.tex.size())) || (rc = alloc_copy(&ctx->pvec, pv.data(), pv.size())) ||
@@ -747,6 +804,8 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   ctx->has_media = ds.has_media ? 1 : 0;
   ctx->has_tri = 0;
   for (const Obj &o : ds.obj) ctx->has_tri |= o.kind == kTriangle ? 1 : 0;
+  ctx->nattr = int32_t(nattr);
+  if (nattr) ctx->has_tri = 2;
   bool simple = ds.med.empty();
   for (const Obj &o : ds.obj) simple = simple && o.inst < 0 && (o.kind == kSphere || o.kind == kMovingSphere);
   for (const Tex &t : ds.tex)
@@ -873,7 +932,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   // the kernel that will run, its static LDS beside the staged bytes, and
   // (persistent) how many of its blocks stay resident with those bytes
   auto kernel_of = [&](auto tri) -> const void * {
-    constexpr bool T = decltype(tri)::value;
+    constexpr int T = decltype(tri)::value;
     return simple                ? (const void *)render_persistent<true, true, true, true>
            : persist && use_grid ? (const void *)render_persistent<true, true, true, false, T>
            : persist && p_objs   ? (const void *)render_persistent<true, true, false, false, T>
@@ -883,7 +942,10 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
            : lds_nodes           ? (const void *)render_kernel<true, true, false, false, T>
                                  : (const void *)render_kernel<true, false, false, false, T>;
   };
-  const void *kfn = ctx->has_tri ? kernel_of(std::true_type{}) : kernel_of(std::false_type{});
+  using Tri0 = std::integral_constant<int, 0>;
+  using Tri1 = std::integral_constant<int, 1>;
+  using Tri2 = std::integral_constant<int, 2>;
+  const void *kfn = ctx->has_tri == 2 ? kernel_of(Tri2{}) : ctx->has_tri ? kernel_of(Tri1{}) : kernel_of(Tri0{});
   {
     hipFuncAttributes fa;
     HIP_TRY(hipFuncGetAttributes(&fa, kfn));
@@ -924,7 +986,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   ctx->last_staging[0] = !use_grid && (persist || lds_nodes) ? 1 : 0;
   ctx->last_staging[1] = use_grid || (persist ? p_objs : lds_objs) ? 1 : 0;
   auto launch_t = [&](auto chunked, auto tri) {
-    constexpr bool C = decltype(chunked)::value, T = decltype(tri)::value;
+    constexpr bool C = decltype(chunked)::value;
+    constexpr int T = decltype(tri)::value;
     if (simple)
       hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (persist && use_grid)
@@ -943,8 +1006,9 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
       hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
   };
   auto launch = [&](auto chunked) {
-    if (ctx->has_tri) launch_t(chunked, std::true_type{});
-    else launch_t(chunked, std::false_type{});
+    if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
+    else if (ctx->has_tri) launch_t(chunked, Tri1{});
+    else launch_t(chunked, Tri0{});
   };
   if (a.nch > 1) {
     const size_t nv = size_t(valid) * W * 3;
@@ -998,7 +1062,8 @@ RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   int *d_n = nullptr;
   HIP_TRY(hipMalloc(&d_rec, size_t(cap) * 12 * sizeof(float)));
   HIP_TRY(hipMalloc(&d_n, sizeof(int)));
-  hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
+  hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n,
+                     ctx->nattr > 0 ? 1 : 0);
   hipError_t e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(n, d_n, sizeof(int), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(rec, d_rec, size_t(*n) * 12 * sizeof(float), hipMemcpyDeviceToHost);
@@ -1048,6 +1113,53 @@ RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64
   (void)hipFree(d_id);
   (void)hipFree(d_face);
   if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_hits: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+                                    float *out_t, float *out_pnuv, int32_t *out_mat) {
+  if (!ctx || (n > 0 && (!rays || !out_id || !out_t || !out_pnuv || !out_mat)) || n < 0)
+    return set_error(RT_EINVAL, "rt_nw_debug_records: bad argument");
+  if (ctx->nobj + ctx->nmed <= 0) return set_error(RT_EINVAL, "no scene uploaded (rt_nw_ctx_set_scene)");
+  if (n == 0) return RT_OK;
+  Guard g(ctx->device);
+  const bool grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
+  const size_t lds = grid ? grid_bytes(ctx) : 0;
+  if (lds > kCuLds) return set_error(RT_EUNSUPPORTED, "rt_nw_debug_records: grid of %zu B exceeds a CU's LDS", lds);
+  float *d_rays = nullptr, *d_t = nullptr, *d_rec = nullptr;
+  unsigned long long *d_keys = nullptr;
+  int32_t *d_id = nullptr, *d_mat = nullptr;
+  hipError_t e = hipMalloc(&d_rays, size_t(n) * 8 * sizeof(float));
+  if (e == hipSuccess && keys) e = hipMalloc(&d_keys, size_t(n) * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(&d_t, size_t(n) * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_rec, size_t(n) * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_id, size_t(n) * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&d_mat, size_t(n) * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, size_t(n) * 8 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const dim3 grd(unsigned((n + 255) / 256)), blk(256);
+    const int has_attr = ctx->nattr > 0 ? 1 : 0;
+    if (grid)
+      hipLaunchKernelGGL(debug_records_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, has_attr,
+                         d_id, d_t, d_rec, d_mat);
+    else
+      hipLaunchKernelGGL(debug_records_kernel<false>, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, has_attr,
+                         d_id, d_t, d_rec, d_mat);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out_id, d_id, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_t, d_t, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_pnuv, d_rec, size_t(n) * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_mat, d_mat, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d_rays);
+  (void)hipFree(d_keys);
+  (void)hipFree(d_t);
+  (void)hipFree(d_rec);
+  (void)hipFree(d_id);
+  (void)hipFree(d_mat);
+  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_records: %s", hipGetErrorString(e));
   return RT_OK;
 }
 

@@ -7,13 +7,17 @@
 //   rtmi_nw_render [--scene 1..8|final|cornell_box|...] [--width W] [--height H]
 //                  [--spp S] [--depth D] [--seed N] [--texture FILE.ppm]
 //                  [--out FILE|-] [--p6] [--rtl]
-//   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--width W] ...
+//   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
+//                  [--obj-texture FILE.ppm] [--width W] ...
 //
 // --obj (exclusive with --scene) renders a Wavefront OBJ mesh
 // (rt_nw_scene_obj_stage): scaled and centred into the box [-1, 1] x [0, 2] x
 // [-1, 1] on a checker ground, one 3 x 3 light of emission 6 at y = 5,
 // background (0.05, 0.07, 0.12), camera from (3.2, 2.4, 4.8) at (0, 1, 0),
-// vfov 30, no aperture.
+// vfov 30, no aperture.  --obj-smooth shades with the file's vn interpolated
+// (--obj-gen-normals: area-weighted vertex normals where the file has none),
+// --obj-texture maps a binary PPM (P6, read as --texture is) onto the mesh by
+// the file's vt (lambertian or metal); none of the three is valid with --scene.
 //
 // --texture is the earth image as a binary PPM (P6; the reference decodes
 // earthmap.jpeg with stb_image, main.cu:497-510 — convert it once, e.g. with
@@ -67,8 +71,8 @@ static bool read_p6(const char *path, std::vector<uint8_t> &px, int &w, int &h) 
 }
 
 int main(int argc, char **argv) {
-  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian";
-  bool scene_given = false;
+  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture;
+  bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0;
   unsigned long long seed = 1984;
   for (int a = 1; a < argc; a++) {
@@ -79,6 +83,9 @@ int main(int argc, char **argv) {
     if (!std::strcmp(argv[a], "--scene")) { scene = need("--scene"); scene_given = true; }
     else if (!std::strcmp(argv[a], "--obj")) obj = need("--obj");
     else if (!std::strcmp(argv[a], "--obj-mat")) obj_mat = need("--obj-mat");
+    else if (!std::strcmp(argv[a], "--obj-smooth")) obj_smooth = true;
+    else if (!std::strcmp(argv[a], "--obj-gen-normals")) obj_gen = true;
+    else if (!std::strcmp(argv[a], "--obj-texture")) obj_texture = need("--obj-texture");
     else if (!std::strcmp(argv[a], "--width")) W = std::atoi(need("--width"));
     else if (!std::strcmp(argv[a], "--height")) H = std::atoi(need("--height"));
     else if (!std::strcmp(argv[a], "--spp")) spp = std::atoi(need("--spp"));
@@ -91,10 +98,13 @@ int main(int argc, char **argv) {
     else {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
                            "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
-                           "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--width W] [--height H] ...\n"
+                           "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]\n"
+                           "          [--obj-texture FILE.ppm] [--width W] [--height H] ...\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
-                           "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n",
+                           "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
+                           "  --obj-smooth: interpolated vn (--obj-gen-normals: generated where missing);\n"
+                           "  --obj-texture: a P6 image mapped by vt (lambertian, metal); all three need --obj\n",
                    argv[0], argv[0]);
       return 2;
     }
@@ -105,6 +115,10 @@ int main(int argc, char **argv) {
   for (int k = 1; k <= 8; ++k)
     if (scene == names[k]) which = k;
   if (!obj.empty() && scene_given) { std::fprintf(stderr, "--scene and --obj are exclusive\n"); return 2; }
+  if (obj.empty() && (obj_smooth || obj_gen || !obj_texture.empty())) {
+    std::fprintf(stderr, "--obj-smooth, --obj-gen-normals and --obj-texture need --obj (not valid with --scene)\n");
+    return 2;
+  }
   const int obj_kind = obj_mat == "lambertian" ? RT_NW_LAMBERTIAN : obj_mat == "metal" ? RT_NW_METAL : obj_mat == "glass" ? RT_NW_DIELECTRIC : -1;
   if (obj_kind < 0) { std::fprintf(stderr, "unknown --obj-mat %s (lambertian, metal, glass)\n", obj_mat.c_str()); return 2; }
   if (obj.empty() && (which < 1 || which > 8)) { std::fprintf(stderr, "unknown scene %s\n", scene.c_str()); return 2; }
@@ -117,12 +131,26 @@ int main(int argc, char **argv) {
     return 2;
   }
 
+  std::vector<uint8_t> oimg;
+  int ow = 0, oh = 0;
+  if (!obj_texture.empty() && !read_p6(obj_texture.c_str(), oimg, ow, oh)) {
+    std::fprintf(stderr, "cannot read P6 texture %s\n", obj_texture.c_str());
+    return 2;
+  }
+  if (!oimg.empty() && obj_kind == RT_NW_DIELECTRIC) { std::fprintf(stderr, "--obj-texture needs --obj-mat lambertian or metal\n"); return 2; }
+
   rt_nw_scene *s = nullptr;
   rt_nw_camera cam;
   int rc;
   if ((rc = rt_nw_scene_create(&s))) return die("rt_nw_scene_create", rc);
   if (!obj.empty()) {
-    if ((rc = rt_nw_scene_obj_stage(s, obj.c_str(), obj_kind, double(W) / H, &cam, nullptr))) return die("rt_nw_scene_obj_stage", rc);
+    const uint32_t flags = (obj_smooth ? RT_NW_MESH_SMOOTH : 0) | (obj_gen ? RT_NW_MESH_GEN_NORMALS : 0) | (oimg.empty() ? 0 : RT_NW_MESH_UV);
+    if (!flags) {
+      if ((rc = rt_nw_scene_obj_stage(s, obj.c_str(), obj_kind, double(W) / H, &cam, nullptr))) return die("rt_nw_scene_obj_stage", rc);
+    } else if ((rc = rt_nw_scene_obj_stage_attr(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh,
+                                                double(W) / H, &cam, nullptr))) {
+      return die("rt_nw_scene_obj_stage_attr", rc);
+    }
   } else if ((rc = rt_nw_scene_preset(s, which, img.empty() ? nullptr : img.data(), iw, ih, double(W) / H,
                                       rtl ? RT_NW_ARGS_RTL : 0, &cam))) {
     return die("rt_nw_scene_preset", rc);

@@ -25,6 +25,8 @@ struct Node {
 struct DeviceScene {
   std::vector<Obj> obj;          // non-media objects, BVH leaf order; aux = twin medium's index in med + 1
   std::vector<int32_t> obj_id;   // insertion index of obj[k]
+  std::vector<TriAttr> attr;     // triangle attribute records (rt_nw_mesh_attr); empty when no object has one
+  std::vector<int32_t> obj_attr; // record of obj[k] or -1; empty when no object has one
   std::vector<Obj> med;          // media, insertion order
   std::vector<int32_t> med_id;   // their insertion indices
   std::vector<Inst> inst;

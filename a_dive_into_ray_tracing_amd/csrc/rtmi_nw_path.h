@@ -478,14 +478,16 @@ __device__ __forceinline__ unsigned nw_test_flop(int kind, bool inst) {
 // invw = 1/dw per axis of the world ray (hit_rect_inv); trw = the world ray's
 // triangle shears Sx, Sy (tri_ray; its Sz is invw's kz component: the same
 // IEEE 1/d), computed per segment.
-// TRI: the scene holds triangles.  Scenes without them run the TRI = false
+// TRI: 0 the scene holds no triangle, 1 it holds triangles, 2 some of them
+// carry an attribute record (TriAttr; read by make_rec alone: the walks of 1
+// and 2 are the same code).  Scenes without triangles run the TRI = 0
 // instantiations, the kernels as they were before triangles existed (the
 // triangle test inside the 64-VGPR BVH kernels cost the final scene 15%,
 // profiles/mesh/README.md).
 // S: a spheres-only scene (rt_nw_ctx_set_scene's check: spheres and moving
 // spheres, no instances, no media, solid and checker textures): the other
 // kinds' code is compiled out — the same arithmetic for the kinds that remain.
-template <bool S = false, bool TRI = false>
+template <bool S = false, int TRI = 0>
 __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V ow, V dw, V invw, float2 trw, float time,
                                            float &t, int &face) {
   if constexpr (S) {
@@ -497,7 +499,7 @@ __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V o
   if (local) to_local(sc.inst[ob.inst], o, d);
   const float tmin = 0.001f;
   const int kind = ob.ka & 255;
-  if constexpr (TRI) {
+  if constexpr (TRI != 0) {
     if (kind == kTriangle) {
       V v0, v1, v2;
       tri_vertices(ob, v0, v1, v2);
@@ -522,8 +524,8 @@ __device__ __forceinline__ bool hit_object(const View &sc, const DevObj &ob, V o
   }
 }
 // the world ray's Sx, Sy for hit_object<S, TRI>
-template <bool TRI> __device__ __forceinline__ float2 tri_world(V d) {
-  if constexpr (TRI) {
+template <int TRI> __device__ __forceinline__ float2 tri_world(V d) {
+  if constexpr (TRI != 0) {
     const TriRay s = tri_ray(d);
     return make_float2(s.sx, s.sy);
   }
@@ -543,7 +545,7 @@ template <bool TRI> __device__ __forceinline__ float2 tri_world(V d) {
 // LDS layout (dynamic shared memory): nodes lo[nnodes], hi[nnodes]; then, when
 // they fit too, the objects (4 float4 each) and their insertion indices.
 extern __shared__ float4 nw_nodes_lds[];
-template <bool LDS_NODES, bool LDS_OBJS, bool TRI = false>
+template <bool LDS_NODES, bool LDS_OBJS, int TRI = 0>
 __device__ __forceinline__ int32_t hit_world_nw(const View &sc, V o, V d, float time, uint64_t seg_key, float &best_t,
                                                 int &best_face, NwCount *cnt) {
   const float4 *nlo = LDS_NODES ? nw_nodes_lds : sc.nlo;
@@ -636,7 +638,7 @@ __host__ __device__ constexpr size_t nw_grid_lds_bytes(int32_t nobj, int32_t nce
 // its coordinate scale), so inside a cell that lists it; an object listed in
 // several cells gives the same t each time.  The objects' boxes cover the
 // whole shutter (moving spheres) and the composed transform (instances).
-template <bool S = false, bool TRI = false>
+template <bool S = false, int TRI = 0>
 __device__ __forceinline__ int32_t hit_world_nw_grid(const View &sc, V o, V d, float time, uint64_t seg_key,
                                                      float &best_t, int &best_face, NwCount *cnt) {
   const DevObj *objs = reinterpret_cast<const DevObj *>(nw_nodes_lds);
@@ -855,8 +857,50 @@ __device__ __forceinline__ Rec make_rec_medium(const View &sc, const Obj &ob, V 
   r.n = mk(1.0f, 0.0f, 0.0f);
   return r;
 }
-template <bool S = false, bool TRI = false>
-__device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, V dw, float time, float t, int face) {
+// ---------------------------------------------------------------------------
+// Triangle attributes (TRI = 2): smooth normals and texture coordinates.
+// Where the records live: the attribute records (TriAttr) follow the object
+// records in the objects' allocation, and the per-leaf-slot locator (the
+// record index of slot k, -1: none) follows the insertion indices in theirs —
+// so View, and with it every kernel's argument block, is what it was without
+// them.  Both are read from global memory, by make_rec alone.
+// THE SPECIFICATION of make_rec for a triangle with an attribute record
+// (tests/native/nw_smooth_ref.cpp restates it); everything in the triangle's
+// local space — o, d the local ray (the world ray of a triangle without an
+// instance), ng the geometric normal of the specification above:
+//   U, V, W, det from tri_edges(o, tri_axes(d), tri_ray(d), v0, v1, v2), the
+//    triangle specification's edge functions recomputed, double fallback
+//    included
+//   b0 = U / det, b1 = V / det, b2 = W / det      (three IEEE divisions, never
+//    1 - b1 - b2: the weights of v0, v1, v2)
+//  normals (flags bit 0; without it n = ng):
+//   per component ns = fmaf(b2, n2, fmaf(b1, n1, b0 * n0))
+//   l2 = dot3(ns, ns)
+//   if !(l2 > 0): n = ng.  Otherwise ns = ns * (1 / sqrt(l2)) per component
+//    (drcp(dsqrt(l2)), as ng is scaled) and the side rule decides:
+//   a = dot3(d, ng), b = dot3(d, ns)
+//   n = ns when (a > 0 and b > 0) or (a < 0 and b < 0), else n = ng
+//    — every material's front / back decision stays the geometric one
+//    (dielectric dn > 0, metal's dot(dir, n) > 0: consistent at grazing angles)
+//   n is never flipped and goes through the instance rotation as ng does.
+//  uvs, only when the material's texture reads u, v (else u = v = 0):
+//   flags bit 1: u = fmaf(b2, uv2.u, fmaf(b1, uv1.u, b0 * uv0.u)), v alike;
+//    passed on unwrapped (the image texture clamps to [0, 1])
+//   without bit 1: u = V / det, v = W / det as for any triangle (= b1, b2)
+// A triangle without an attribute record keeps the record above exactly.
+// ---------------------------------------------------------------------------
+struct AttrView {
+  const TriAttr *rec;       // null: the scene has no attribute record
+  const int32_t *of_slot;   // per leaf-order slot: index into rec, or -1
+};
+__device__ __forceinline__ AttrView attr_view_of(const View &sc) {
+  return AttrView{reinterpret_cast<const TriAttr *>(sc.obj + sc.nobj), sc.obj_id + sc.nobj};
+}
+
+// slot: the object's leaf-order slot (read only by TRI = 2, with av)
+template <bool S = false, int TRI = 0>
+__device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, V dw, float time, float t, int face,
+                                        AttrView av = AttrView{nullptr, nullptr}, int32_t slot = 0) {
   Rec r;
   r.mat = ob.mat;
   r.u = 0.0f;
@@ -884,14 +928,43 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
     const float inv_r = drcp(ob.g0[3]);
     n = mk(inv_r * (p.x - c.x), inv_r * (p.y - c.y), inv_r * (p.z - c.z));
     if (need_uv) sphere_uv(n, r.u, r.v);
-  } else if (TRI && okind == kTriangle) {
+  } else if (TRI != 0 && okind == kTriangle) {
     V v0, v1, v2;
     tri_vertices(ob, v0, v1, v2);
     const V e1 = sub3(v1, v0), e2 = sub3(v2, v0);
     const V c = mk(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
     const float inv_len = drcp(dsqrt(dot3(c, c)));
     n = mk(c.x * inv_len, c.y * inv_len, c.z * inv_len);
-    if (need_uv) {
+    int32_t ai = -1;
+    if constexpr (TRI == 2) ai = av.rec ? av.of_slot[slot] : -1;
+    if (TRI == 2 && ai >= 0) {  // the specification above
+      const TriAttr &ta = av.rec[ai];
+      const int aflags = ta.flags;
+      float U, Vv, W, det, T;
+      (void)tri_edges(o, tri_axes(d), tri_ray(d), v0, v1, v2, U, Vv, W, det, T);
+      const float b0 = U / det, b1 = Vv / det, b2 = W / det;
+      if (aflags & 1) {
+        V ns = mk(__builtin_fmaf(b2, ta.n[6], __builtin_fmaf(b1, ta.n[3], b0 * ta.n[0])),
+                  __builtin_fmaf(b2, ta.n[7], __builtin_fmaf(b1, ta.n[4], b0 * ta.n[1])),
+                  __builtin_fmaf(b2, ta.n[8], __builtin_fmaf(b1, ta.n[5], b0 * ta.n[2])));
+        const float l2 = dot3(ns, ns);
+        if (l2 > 0.0f) {
+          const float inv_l = drcp(dsqrt(l2));
+          ns = mk(ns.x * inv_l, ns.y * inv_l, ns.z * inv_l);
+          const float a = dot3(d, n), b = dot3(d, ns);
+          if ((a > 0.0f && b > 0.0f) || (a < 0.0f && b < 0.0f)) n = ns;
+        }
+      }
+      if (need_uv) {
+        if (aflags & 2) {
+          r.u = __builtin_fmaf(b2, ta.uv[4], __builtin_fmaf(b1, ta.uv[2], b0 * ta.uv[0]));
+          r.v = __builtin_fmaf(b2, ta.uv[5], __builtin_fmaf(b1, ta.uv[3], b0 * ta.uv[1]));
+        } else {
+          r.u = b1;
+          r.v = b2;
+        }
+      }
+    } else if (need_uv) {
       float U, Vv, W, det, T;
       (void)tri_edges(o, tri_axes(d), tri_ray(d), v0, v1, v2, U, Vv, W, det, T);
       r.u = Vv / det;

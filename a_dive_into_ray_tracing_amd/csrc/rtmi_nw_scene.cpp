@@ -28,6 +28,7 @@ enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4
 struct SNode {
   int type = kPrim;
   int32_t kind = 0, mat = -1;  // kPrim
+  int32_t attr = -1;           // kPrim, a triangle: its attribute record (rt_nw_scene::attr) or -1
   double g[12] = {0};          // kPrim geometry, double (layout of Obj g0..g2)
   std::vector<int32_t> kids;   // kGroup
   int32_t child = -1;          // kTranslate / kRotate / kMediumNode
@@ -102,12 +103,14 @@ struct rt_nw_scene {
   std::vector<Image> image;
   std::vector<Mat> mat;
   std::vector<SNode> nodes;
+  std::vector<TriAttr> attr;  // triangle attribute records (rt_nw_mesh_attr), creation order
   std::vector<int32_t> world;
   float background[3] = {0.f, 0.f, 0.f};
   // flattened view (rt_nw_scene_flat), insertion order
   bool flat_valid = false;
   std::vector<Obj> flat_obj;
   std::vector<int32_t> flat_src;  // the SNode a flattened object came from (twin detection)
+  std::vector<int32_t> flat_attr; // its attribute record or -1 (rt_nw_scene_flat_attr)
   std::vector<Bounds> flat_bounds;
   std::vector<Inst> flat_inst;
 };
@@ -287,6 +290,7 @@ struct Flattener {
         o.aux = 0;
         s->flat_obj.push_back(o);
         s->flat_src.push_back(id);
+        s->flat_attr.push_back(n.attr);
         s->flat_bounds.push_back(world_bounds(local_bounds(n, n.kind), x));
         return;
       }
@@ -316,6 +320,7 @@ struct Flattener {
         o.inst = inst_of(xb);
         s->flat_obj.push_back(o);
         s->flat_src.push_back(prim);
+        s->flat_attr.push_back(-1);
         s->flat_bounds.push_back(world_bounds(local_bounds(b, b.kind), xb));
         return;
       }
@@ -327,6 +332,7 @@ int flatten(rt_nw_scene *s) {
   if (s->flat_valid) return RT_OK;
   s->flat_obj.clear();
   s->flat_src.clear();
+  s->flat_attr.clear();
   s->flat_bounds.clear();
   s->flat_inst.clear();
   Flattener f{s, {}, RT_OK};
@@ -607,9 +613,18 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   out.nodes = std::move(bvh.nodes);
   out.obj.resize(n);
   out.obj_id.resize(n);
+  out.attr.clear();
+  out.obj_attr.clear();
+  for (int k = 0; k < n; ++k)
+    if (s->flat_attr[bvh.order[k]] >= 0) {  // some object carries an attribute record: the locator exists
+      out.attr = s->attr;
+      out.obj_attr.resize(n);
+      break;
+    }
   for (int k = 0; k < n; ++k) {
     out.obj[k] = s->flat_obj[bvh.order[k]];
     out.obj_id[k] = bvh.order[k];
+    if (!out.obj_attr.empty()) out.obj_attr[k] = s->flat_attr[bvh.order[k]];
     if (out.obj[k].aux > 0) out.obj[k].aux = med_index[out.obj[k].aux - 1] + 1;  // twin -> media-list index + 1
   }
   build_obj_grid(s->flat_bounds, margin, bvh.order, out);
@@ -801,7 +816,8 @@ namespace {
 // as floats (what the device tests).  Collinear vertices are allowed: such a
 // triangle is never hit (build_device_scene leaves it out of the BVH and the
 // grid, collinear_triangle).
-int add_triangle(rt_nw_scene *s, const double *v0, const double *v1, const double *v2, int32_t mat, const char *who) {
+int add_triangle(rt_nw_scene *s, const double *v0, const double *v1, const double *v2, int32_t mat, const char *who,
+                 int32_t attr = -1) {
   const double *v[3] = {v0, v1, v2};
   float f[3][3];
   for (int k = 0; k < 3; ++k)
@@ -817,21 +833,57 @@ int add_triangle(rt_nw_scene *s, const double *v0, const double *v1, const doubl
   SNode n;
   n.kind = kTriangle;
   n.mat = mat;
+  n.attr = attr;
   for (int k = 0; k < 3; ++k)
     for (int a = 0; a < 3; ++a) n.g[3 * k + a] = v[k][a];
   return add_node(s, n);
 }
+
+// Corner attributes of a mesh (rt_nw_mesh_attr, rt_nw_load_obj_attr); flags 0:
+// none, add_mesh builds what rt_nw_mesh builds.
+struct MeshAttr {
+  uint32_t flags = 0;           // RT_NW_MESH_*
+  const double *uvs = nullptr;  // RT_NW_MESH_UV: n_uvs pairs
+  int32_t n_uvs = 0;
+  const int32_t *uvidx = nullptr;  // three per triangle; null: the vertex indices
+  bool uv_missing = false;         // a uvidx entry of -1 is a corner without uv (an OBJ face): no uvs for the triangle
+};
 
 // The shared builder of rt_nw_mesh and rt_nw_load_obj.  nidx entries may be
 // -1 only when allow_missing (an OBJ face without normals keeps its winding).
 // line_of (may be null): the file line of each triangle, for error messages.
 int add_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri, int32_t n_tris,
              const double *normals, int32_t n_normals, const int32_t *nidx, bool allow_missing, int32_t mat,
-             const int32_t *line_of, const char *who) {
+             const int32_t *line_of, const char *who, const MeshAttr &at = MeshAttr{}) {
   SNode grp;
   grp.type = kGroup;
   grp.kids.reserve(size_t(n_tris));
   std::string where;
+  const bool smooth = (at.flags & RT_NW_MESH_SMOOTH) != 0, want_uv = (at.flags & RT_NW_MESH_UV) != 0;
+  // RT_NW_MESH_GEN_NORMALS: per vertex index the sum of cross(v1 - v0, v2 - v0)
+  // over the triangles of this call that use it, from the vertices as given
+  // (before any exchange), so area-weighted.  (A triangle with an index out of
+  // range is skipped here; the loop below refuses it.)
+  std::vector<double> gen;
+  if (smooth && (at.flags & RT_NW_MESH_GEN_NORMALS)) {
+    gen.assign(3 * size_t(n_verts), 0.0);
+    for (int32_t t = 0; t < n_tris; ++t) {
+      const int32_t *ix = tri + 3 * size_t(t);
+      if (ix[0] < 0 || ix[0] >= n_verts || ix[1] < 0 || ix[1] >= n_verts || ix[2] < 0 || ix[2] >= n_verts) continue;
+      const double *v0 = verts + 3 * size_t(ix[0]), *v1 = verts + 3 * size_t(ix[1]), *v2 = verts + 3 * size_t(ix[2]);
+      const double e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+      const double fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+      for (int c = 0; c < 3; ++c)
+        for (int a = 0; a < 3; ++a) gen[3 * size_t(ix[c]) + a] += fn[a];
+    }
+  }
+  // v / |v| in double, rounded to float; false: zero or not finite
+  auto unit_f = [](const double *v, float *out) {
+    const double len = std::hypot(v[0], v[1], v[2]);
+    if (!(len > 0) || !std::isfinite(len)) return false;
+    for (int a = 0; a < 3; ++a) out[a] = float(v[a] / len);
+    return true;
+  };
   for (int32_t t = 0; t < n_tris; ++t) {
     if (line_of) where = std::string(who) + ": line " + std::to_string(line_of[t]);
     else where = std::string(who) + ": triangle " + std::to_string(t);
@@ -839,6 +891,7 @@ int add_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t
     for (int c = 0; c < 3; ++c)
       if (ix[c] < 0 || ix[c] >= n_verts) return set_error(RT_EINVAL, "%s: vertex index %d out of range", where.c_str(), ix[c]);
     const double *v0 = verts + 3 * size_t(ix[0]), *v1 = verts + 3 * size_t(ix[1]), *v2 = verts + 3 * size_t(ix[2]);
+    bool swapped = false;
     if (normals) {
       const int32_t *nx = nidx ? nidx + 3 * size_t(t) : ix;
       double ns[3] = {0, 0, 0};
@@ -851,10 +904,56 @@ int add_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t
       if (have) {  // front = the side of the normals' sum (the OBJ convention)
         const double e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
         const double fn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        if (fn[0] * ns[0] + fn[1] * ns[1] + fn[2] * ns[2] < 0) std::swap(v1, v2);
+        if (fn[0] * ns[0] + fn[1] * ns[1] + fn[2] * ns[2] < 0) {
+          std::swap(v1, v2);
+          swapped = true;
+        }
       }
     }
-    const int id = add_triangle(s, v0, v1, v2, mat, where.c_str());
+    int32_t attr = -1;
+    if (smooth || want_uv) {
+      TriAttr ta{};
+      if (smooth) {  // every corner needs a normal: the explicit one, else (GEN_NORMALS) the generated one
+        const int32_t *nx = !normals ? nullptr : nidx ? nidx + 3 * size_t(t) : ix;
+        bool all = true;
+        for (int c = 0; c < 3 && all; ++c) {
+          if (nx && nx[c] >= 0) {  // (range-checked above)
+            const double *nv = normals + 3 * size_t(nx[c]);
+            for (int a = 0; a < 3; ++a)
+              if (!std::isfinite(float(nv[a]))) return set_error(RT_EINVAL, "%s: normal %d not finite", where.c_str(), nx[c]);
+            if (!unit_f(nv, ta.n + 3 * c)) return set_error(RT_EINVAL, "%s: normal %d has zero length", where.c_str(), nx[c]);
+          } else {
+            all = !gen.empty() && unit_f(gen.data() + 3 * size_t(ix[c]), ta.n + 3 * c);
+          }
+        }
+        if (all) ta.flags |= 1;
+      }
+      if (want_uv) {
+        const int32_t *ux = at.uvidx ? at.uvidx + 3 * size_t(t) : ix;
+        bool all = true;
+        for (int c = 0; c < 3; ++c) {
+          if (ux[c] == -1 && at.uv_missing) { all = false; continue; }
+          if (ux[c] < 0 || ux[c] >= at.n_uvs) return set_error(RT_EINVAL, "%s: uv index %d out of range", where.c_str(), ux[c]);
+          for (int a = 0; a < 2; ++a) {
+            ta.uv[2 * c + a] = float(at.uvs[2 * size_t(ux[c]) + a]);
+            if (!std::isfinite(ta.uv[2 * c + a])) return set_error(RT_EINVAL, "%s: uv %d not finite", where.c_str(), ux[c]);
+          }
+        }
+        if (all) ta.flags |= 2;
+      }
+      if (swapped) {  // v1 and v2 were exchanged: their normals and uvs go with them
+        for (int a = 0; a < 3; ++a) std::swap(ta.n[3 + a], ta.n[6 + a]);
+        for (int a = 0; a < 2; ++a) std::swap(ta.uv[2 + a], ta.uv[4 + a]);
+      }
+      if (!(ta.flags & 1)) std::fill(ta.n, ta.n + 9, 0.f);
+      if (!(ta.flags & 2)) std::fill(ta.uv, ta.uv + 6, 0.f);
+      if (ta.flags) {
+        if (s->attr.size() >= (size_t(1) << 27)) return set_error(RT_EINVAL, "%s: too many attribute records", who);
+        s->attr.push_back(ta);
+        attr = int32_t(s->attr.size()) - 1;
+      }
+    }
+    const int id = add_triangle(s, v0, v1, v2, mat, where.c_str(), attr);
     if (id < 0) return id;
     grp.kids.push_back(id);
   }
@@ -876,19 +975,35 @@ RTMI_EXPORT int rt_nw_mesh(rt_nw_scene *s, const double *verts, int32_t n_verts,
   return add_mesh(s, verts, n_verts, tri_idx, n_tris, normals, n_normals, normal_idx, false, mat, nullptr, "rt_nw_mesh");
 }
 
+RTMI_EXPORT int rt_nw_mesh_attr(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri_idx, int32_t n_tris,
+                                const double *normals, int32_t n_normals, const int32_t *normal_idx, const double *uvs,
+                                int32_t n_uvs, const int32_t *uv_idx, uint32_t flags, int32_t mat) {
+  if (!s || !verts || !tri_idx || n_verts < 1 || n_tris < 1 || !valid_mat(s, mat) || (normals && n_normals < 1) ||
+      (!normals && normal_idx) || (flags & ~uint32_t(RT_NW_MESH_SMOOTH | RT_NW_MESH_UV | RT_NW_MESH_GEN_NORMALS)) ||
+      ((flags & RT_NW_MESH_UV) && (!uvs || n_uvs < 1)) || (!uvs && uv_idx))
+    return set_error(RT_EINVAL, "rt_nw_mesh_attr: bad argument");
+  MeshAttr at;
+  at.flags = flags;
+  at.uvs = uvs;
+  at.n_uvs = n_uvs;
+  at.uvidx = uv_idx;
+  return add_mesh(s, verts, n_verts, tri_idx, n_tris, normals, n_normals, normal_idx, false, mat, nullptr, "rt_nw_mesh_attr", at);
+}
+
 // Wavefront OBJ: v, vn and f (a, a/t, a//n, a/t/n; negative indices count
 // back from the latest vertex / normal; polygons fan-triangulated in the
-// file's winding).  Every other statement is ignored.
+// file's winding) and, for rt_nw_load_obj_attr under RT_NW_MESH_UV only, vt
+// and the t of a corner.  Every other statement is ignored.
 namespace {
 struct ObjFile {
-  std::vector<double> verts, normals;
-  std::vector<int32_t> tri, nidx, line_of;  // nidx: -1 for a corner without a normal
+  std::vector<double> verts, normals, uvs;
+  std::vector<int32_t> tri, nidx, tidx, line_of;  // nidx / tidx: -1 for a corner without a normal / uv
 };
-int parse_obj(const char *path, ObjFile &out) {
+int parse_obj(const char *path, ObjFile &out, bool want_uv = false) {
   FILE *f = std::fopen(path, "rb");
   if (!f) return set_error(RT_EIO, "rt_nw_load_obj: cannot open %s", path);
-  std::vector<double> &verts = out.verts, &normals = out.normals;
-  std::vector<int32_t> &tri = out.tri, &nidx = out.nidx, &line_of = out.line_of;
+  std::vector<double> &verts = out.verts, &normals = out.normals, &uvs = out.uvs;
+  std::vector<int32_t> &tri = out.tri, &nidx = out.nidx, &tidx = out.tidx, &line_of = out.line_of;
   std::string line;
   int lineno = 0, rc = RT_OK;
   // one number of a v / vn statement: the whole token must parse
@@ -942,19 +1057,30 @@ int parse_obj(const char *path, ObjFile &out) {
       }
       std::vector<double> &dst = is_v ? verts : normals;
       dst.insert(dst.end(), x, x + 3);
+    } else if (want_uv && p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t' || !p[2])) {
+      p += 2;  // vt u [v [w]]: v defaults to 0, w is ignored
+      double x[3] = {0, 0, 0};
+      int got = 0;
+      while (got < 3 && number(p, x[got])) ++got;
+      while (*p == ' ' || *p == '\t') ++p;
+      if (got < 1 || *p) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed number", path, lineno); break; }
+      uvs.insert(uvs.end(), x, x + 2);
     } else if (is_f) {
       p += 1;
-      std::vector<int32_t> cv, cn;
-      const long nv = long(verts.size() / 3), nn = long(normals.size() / 3);
+      std::vector<int32_t> cv, cn, ct;
+      const long nv = long(verts.size() / 3), nn = long(normals.size() / 3), nt = long(uvs.size() / 2);
       for (;;) {
         while (*p == ' ' || *p == '\t') ++p;
         if (!*p) break;
         long iv = 0, in = 0, it = 0;
-        bool has_n = false;
+        bool has_n = false, has_t = false;
         if (!integer(p, iv)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
         if (*p == '/') {
           ++p;
-          if (*p != '/' && !integer(p, it)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+          if (*p != '/') {
+            if (!integer(p, it)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
+            has_t = true;
+          }
           if (*p == '/') {
             ++p;
             if (!integer(p, in)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: malformed face index", path, lineno); break; }
@@ -965,16 +1091,25 @@ int parse_obj(const char *path, ObjFile &out) {
         const long av = iv < 0 ? nv + iv : iv - 1, an = !has_n ? -1 : in < 0 ? nn + in : in - 1;
         if (iv == 0 || av < 0 || av >= nv) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: vertex index %ld out of range", path, lineno, iv); break; }
         if (has_n && (in == 0 || an < 0 || an >= nn)) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: normal index %ld out of range", path, lineno, in); break; }
+        long at = -1;  // the t of a corner is read under RT_NW_MESH_UV only
+        if (want_uv && has_t) {
+          at = it < 0 ? nt + it : it - 1;
+          if (it == 0 || at < 0 || at >= nt) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: texture index %ld out of range", path, lineno, it); break; }
+        }
         cv.push_back(int32_t(av));
         cn.push_back(int32_t(an));
+        ct.push_back(int32_t(at));
       }
       if (rc) break;
       if (cv.size() < 3) { rc = set_error(RT_EINVAL, "rt_nw_load_obj: %s: line %d: face with fewer than three corners", path, lineno); break; }
+      // a face with a corner lacking t gets no uvs
+      const bool face_uv = std::find(ct.begin(), ct.end(), -1) == ct.end();
       for (size_t k = 1; k + 1 < cv.size(); ++k) {  // fan about the first corner
         const size_t c3[3] = {0, k, k + 1};
         for (size_t q : c3) {
           tri.push_back(cv[q]);
           nidx.push_back(cn[q]);
+          tidx.push_back(face_uv ? ct[q] : -1);
         }
         line_of.push_back(lineno);
       }
@@ -989,16 +1124,34 @@ int parse_obj(const char *path, ObjFile &out) {
   if (tri.empty()) return set_error(RT_EINVAL, "rt_nw_load_obj: %s: no faces", path);
   return RT_OK;
 }
-int add_obj_mesh(rt_nw_scene *s, const char *path, const ObjFile &o, int32_t mat, int32_t *n_tris) {
+int add_obj_mesh(rt_nw_scene *s, const char *path, const ObjFile &o, int32_t mat, int32_t *n_tris, uint32_t flags = 0) {
   const int32_t nt = int32_t(o.tri.size() / 3);
   const std::string who = std::string("rt_nw_load_obj: ") + path;
   const bool nrm = !o.normals.empty();
+  MeshAttr at;
+  at.flags = flags;
+  if (flags & RT_NW_MESH_UV) {
+    at.uvs = o.uvs.data();
+    at.n_uvs = int32_t(o.uvs.size() / 2);
+    at.uvidx = o.tidx.data();
+    at.uv_missing = true;
+  }
   const int id = add_mesh(s, o.verts.data(), int32_t(o.verts.size() / 3), o.tri.data(), nt, nrm ? o.normals.data() : nullptr,
-                          int32_t(o.normals.size() / 3), nrm ? o.nidx.data() : nullptr, true, mat, o.line_of.data(), who.c_str());
+                          int32_t(o.normals.size() / 3), nrm ? o.nidx.data() : nullptr, true, mat, o.line_of.data(), who.c_str(), at);
   if (id >= 0 && n_tris) *n_tris = nt;
   return id;
 }
+bool mesh_flags_ok(uint32_t flags) {
+  return !(flags & ~uint32_t(RT_NW_MESH_SMOOTH | RT_NW_MESH_UV | RT_NW_MESH_GEN_NORMALS));
+}
 }  // namespace
+
+RTMI_EXPORT int rt_nw_load_obj_attr(rt_nw_scene *s, const char *path, int32_t mat, uint32_t flags, int32_t *n_tris) {
+  if (!s || !path || !valid_mat(s, mat) || !mesh_flags_ok(flags)) return set_error(RT_EINVAL, "rt_nw_load_obj_attr: bad argument");
+  ObjFile o;
+  if (int rc = parse_obj(path, o, (flags & RT_NW_MESH_UV) != 0)) return rc;
+  return add_obj_mesh(s, path, o, mat, n_tris, flags);
+}
 
 RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, int32_t *n_tris) {
   if (!s || !path || !valid_mat(s, mat)) return set_error(RT_EINVAL, "rt_nw_load_obj: bad argument");
@@ -1013,13 +1166,19 @@ RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, in
 // one 3 x 3 xz_rect light of emission 6 at y = 5 and the background (0.05,
 // 0.07, 0.12).  Camera: from (3.2, 2.4, 4.8) at the box centre (0, 1, 0),
 // vfov 30, no aperture.
-RTMI_EXPORT int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, double aspect, rt_nw_camera *cam,
-                                      int32_t *n_tris) {
-  if (!s || !path || !cam || !(aspect > 0)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
+// rt_nw_scene_obj_stage_attr: the same stage with the mesh loaded under `flags`
+// (rt_nw_load_obj_attr) and, when rgb is given, that image as the texture of
+// the mesh's lambertian or metal material.
+namespace {
+int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb, int32_t w, int32_t h,
+              double aspect, rt_nw_camera *cam, int32_t *n_tris) {
+  if (!s || !path || !cam || !(aspect > 0) || !mesh_flags_ok(flags)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
   if (mat_kind != RT_NW_LAMBERTIAN && mat_kind != RT_NW_METAL && mat_kind != RT_NW_DIELECTRIC)
     return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: material must be lambertian, metal or dielectric");
+  if (rgb && mat_kind == RT_NW_DIELECTRIC) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: a dielectric takes no texture image");
+  if (rgb && (w <= 0 || h <= 0)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad image size");
   ObjFile o;
-  if (int rc = parse_obj(path, o)) return rc;
+  if (int rc = parse_obj(path, o, (flags & RT_NW_MESH_UV) != 0)) return rc;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int32_t ix : o.tri)  // the vertices the faces use
     for (int a = 0; a < 3; ++a) {
@@ -1035,11 +1194,13 @@ RTMI_EXPORT int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t 
     if (v < 0 && rc == RT_OK) rc = v;
     return v;
   };
-  const int mat = mat_kind == RT_NW_LAMBERTIAN ? chk(rt_nw_mat_lambertian(s, chk(rt_nw_tex_solid(s, 0.7, 0.35, 0.2))))
-                  : mat_kind == RT_NW_METAL    ? chk(rt_nw_mat_metal(s, chk(rt_nw_tex_solid(s, 0.8, 0.8, 0.85)), 0.05))
-                                               : chk(rt_nw_mat_dielectric(s, 1.5));
+  const int mat = mat_kind == RT_NW_LAMBERTIAN
+                      ? chk(rt_nw_mat_lambertian(s, chk(rgb ? rt_nw_tex_image(s, rgb, w, h) : rt_nw_tex_solid(s, 0.7, 0.35, 0.2))))
+                  : mat_kind == RT_NW_METAL
+                      ? chk(rt_nw_mat_metal(s, chk(rgb ? rt_nw_tex_image(s, rgb, w, h) : rt_nw_tex_solid(s, 0.8, 0.8, 0.85)), 0.05))
+                      : chk(rt_nw_mat_dielectric(s, 1.5));
   if (rc) return rc;
-  const int mesh = chk(add_obj_mesh(s, path, o, mat, n_tris));
+  const int mesh = chk(add_obj_mesh(s, path, o, mat, n_tris, flags));
   const double gc[3] = {0, -1000, 0};
   const int ground = chk(rt_nw_sphere(s, gc, 1000, chk(rt_nw_mat_lambertian(s, chk(rt_nw_tex_checker(
                                                       s, chk(rt_nw_tex_solid(s, 0.2, 0.3, 0.1)), chk(rt_nw_tex_solid(s, 0.9, 0.9, 0.9))))))));
@@ -1053,6 +1214,18 @@ RTMI_EXPORT int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t 
   const double from[3] = {3.2, 2.4, 4.8}, at[3] = {0, 1, 0}, vup[3] = {0, 1, 0};
   const double dist = std::sqrt(3.2 * 3.2 + 1.4 * 1.4 + 4.8 * 4.8);
   return rt_nw_camera_init(cam, from, at, vup, 30.0, aspect, 0.0, dist, 0.0, 1.0);
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, double aspect, rt_nw_camera *cam,
+                                      int32_t *n_tris) {
+  return obj_stage(s, path, mat_kind, 0, nullptr, 0, 0, aspect, cam, n_tris);
+}
+
+RTMI_EXPORT int rt_nw_scene_obj_stage_attr(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags,
+                                           const uint8_t *rgb, int32_t w, int32_t h, double aspect, rt_nw_camera *cam,
+                                           int32_t *n_tris) {
+  return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris);
 }
 
 RTMI_EXPORT int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex) {
@@ -1150,6 +1323,15 @@ RTMI_EXPORT int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out) {
   out->image_px = s->image_px.data();
   out->image_bytes = int64_t(s->image_px.size());
   for (int c = 0; c < 3; ++c) out->background[c] = s->background[c];
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_scene_flat_attr(rt_nw_scene *s, int32_t *n_attr, const float **attr, const int32_t **attr_of_obj) {
+  if (!s || !n_attr || !attr || !attr_of_obj) return set_error(RT_EINVAL, "null");
+  if (int rc = flatten(s)) return rc;
+  *n_attr = int32_t(s->attr.size());
+  *attr = reinterpret_cast<const float *>(s->attr.data());
+  *attr_of_obj = s->flat_attr.data();
   return RT_OK;
 }
 

@@ -44,6 +44,16 @@ struct DevObj {
   int32_t inst;
 };
 static_assert(sizeof(DevObj) == 48, "DevObj layout");
+// Per-corner attributes of a triangle built with RT_NW_MESH_SMOOTH / _UV (64 B;
+// rt_nw_scene_flat_attr exposes these records as they are), in the winding
+// the builder settled.  Global memory only: a triangle's record is read once
+// per segment, when its hit record is made (make_rec), never by a walk.
+struct TriAttr {
+  float n[9];     // unit normals of v0, v1, v2 (flags bit 0)
+  float uv[6];    // texture coordinates of v0, v1, v2 (flags bit 1)
+  int32_t flags;  // bit 0: normals present, bit 1: uvs present
+};
+static_assert(sizeof(TriAttr) == 64, "TriAttr layout");
 struct Inst {  // 32 B; world = translate(rotate_y(local)) (hittable.h:49-189)
   float c, s;      // cos, sin of the composed rotate_y angle
   float off[3];    // composed translation

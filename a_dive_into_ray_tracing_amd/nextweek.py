@@ -113,10 +113,14 @@ class Scene:
         """A two-sided, watertight triangle; counter-clockwise is front."""
         return _id(load().rt_nw_triangle(self._h, _v3(v0), _v3(v1), _v3(v2), mat), "rt_nw_triangle")
 
-    def mesh(self, verts, faces, normals=None, mat=None, normal_faces=None):
+    def mesh(self, verts, faces, normals=None, mat=None, normal_faces=None, uvs=None, uv_faces=None, smooth=False,
+             gen_normals=False):
         """Triangles `faces` (n x 3 vertex indices) over `verts` (m x 3) as
         one handle; `normals` (k x 3), indexed by `normal_faces` (n x 3) or,
-        without it, by the vertex indices, fix the winding (rt_nw_mesh)."""
+        without it, by the vertex indices, fix the winding (rt_nw_mesh).
+        smooth: shade with the interpolated normals (gen_normals: area-weighted
+        vertex normals where none is given); uvs (k x 2), indexed by uv_faces
+        or the vertex indices: texture coordinates (rt_nw_mesh_attr)."""
         if mat is None:
             raise TypeError("Scene.mesh: mat is required")
         v = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
@@ -125,15 +129,48 @@ class Scene:
         nf = None if normal_faces is None else np.ascontiguousarray(normal_faces, np.int32).reshape(-1, 3)
         if nf is not None and len(nf) != len(f):
             raise ValueError("Scene.mesh: normal_faces must have one row per face")
-        return _id(load().rt_nw_mesh(self._h, v.ctypes.data_as(_dp), len(v), f.ctypes.data_as(_ip), len(f),
-                                     None if nrm is None else nrm.ctypes.data_as(_dp), 0 if nrm is None else len(nrm),
-                                     None if nf is None else nf.ctypes.data_as(_ip), mat), "rt_nw_mesh")
+        if uvs is None and uv_faces is None and not smooth and not gen_normals:
+            return _id(load().rt_nw_mesh(self._h, v.ctypes.data_as(_dp), len(v), f.ctypes.data_as(_ip), len(f),
+                                         None if nrm is None else nrm.ctypes.data_as(_dp), 0 if nrm is None else len(nrm),
+                                         None if nf is None else nf.ctypes.data_as(_ip), mat), "rt_nw_mesh")
+        uv = None if uvs is None else np.ascontiguousarray(uvs, np.float64).reshape(-1, 2)
+        uf = None if uv_faces is None else np.ascontiguousarray(uv_faces, np.int32).reshape(-1, 3)
+        if uf is not None and len(uf) != len(f):
+            raise ValueError("Scene.mesh: uv_faces must have one row per face")
+        return self.mesh_attr(v, f, nrm, nf, uv, uf, _mesh_flags(smooth, uv is not None, gen_normals), mat)
 
-    def load_obj(self, path, mat):
-        """A Wavefront OBJ file as one mesh (rt_nw_load_obj): (handle, triangle count)."""
+    def mesh_attr(self, v, f, nrm, nf, uv, uf, flags, mat):
+        """rt_nw_mesh_attr as it is (contiguous arrays or None, RT_NW_MESH_* flags)."""
+        return _id(load().rt_nw_mesh_attr(self._h, v.ctypes.data_as(_dp), len(v), f.ctypes.data_as(_ip), len(f),
+                                          None if nrm is None else nrm.ctypes.data_as(_dp), 0 if nrm is None else len(nrm),
+                                          None if nf is None else nf.ctypes.data_as(_ip),
+                                          None if uv is None else uv.ctypes.data_as(_dp), 0 if uv is None else len(uv),
+                                          None if uf is None else uf.ctypes.data_as(_ip), flags, mat), "rt_nw_mesh_attr")
+
+    def load_obj(self, path, mat, smooth=False, uv=False, gen_normals=False):
+        """A Wavefront OBJ file as one mesh: (handle, triangle count).  smooth /
+        gen_normals: shade with the file's vn (generated where missing); uv:
+        read vt and the corners' t (rt_nw_load_obj_attr); none of them:
+        rt_nw_load_obj."""
         n = C.c_int32()
-        h = _id(load().rt_nw_load_obj(self._h, str(path).encode(), mat, C.byref(n)), "rt_nw_load_obj")
+        if not (smooth or uv or gen_normals):
+            h = _id(load().rt_nw_load_obj(self._h, str(path).encode(), mat, C.byref(n)), "rt_nw_load_obj")
+        else:
+            h = _id(load().rt_nw_load_obj_attr(self._h, str(path).encode(), mat, _mesh_flags(smooth, uv, gen_normals),
+                                               C.byref(n)), "rt_nw_load_obj_attr")
         return h, n.value
+
+    def flat_attr(self):
+        """The triangle attribute records beside flat() (rt_nw_scene_flat_attr):
+        {"attr": float32 n x 16 (normals 9, uvs 6, flags as int bits),
+        "attr_of_obj": int32 per flattened object, -1: none}."""
+        n, a, o = C.c_int32(), _fp(), _ip()
+        check(load().rt_nw_scene_flat_attr(self._h, C.byref(n), C.byref(a), C.byref(o)), "rt_nw_scene_flat_attr")
+        fl = RtNwFlat()
+        check(load().rt_nw_scene_flat(self._h, C.byref(fl)), "rt_nw_scene_flat")
+        attr = np.ctypeslib.as_array(a, shape=(16 * n.value,)).copy() if n.value else np.zeros(0, np.float32)
+        of = np.ctypeslib.as_array(o, shape=(fl.n_obj,)).copy() if fl.n_obj else np.zeros(0, np.int32)
+        return {"attr": attr.astype(np.float32).reshape(-1, 16), "attr_of_obj": of.astype(np.int32)}
 
     def constant_medium(self, boundary, density, tex):
         return _id(load().rt_nw_constant_medium(self._h, boundary, float(density), tex), "rt_nw_constant_medium")
@@ -210,15 +247,32 @@ def preset(which, image=None, aspect=1.0, rtl=False):
     return s, cam
 
 
-def obj_stage(path, mat="lambertian", aspect=1.0):
-    """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera
-    (rt_nw_scene_obj_stage): (scene, camera, triangle count)."""
+def _mesh_flags(smooth, uv, gen_normals):
+    """RT_NW_MESH_SMOOTH | _UV | _GEN_NORMALS."""
+    return (1 if smooth else 0) | (2 if uv else 0) | (4 if gen_normals else 0)
+
+
+def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None):
+    """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera:
+    (scene, camera, triangle count).  smooth / gen_normals as Scene.load_obj;
+    texture (h x w x 3 uint8): the mesh's texture, mapped by the file's vt
+    (rt_nw_scene_obj_stage_attr; none of them: rt_nw_scene_obj_stage)."""
     kind = {"lambertian": 0, "metal": 1, "glass": 2, "dielectric": 2}[mat]
     s = Scene()
     cam = RtNwCamera()
     n = C.c_int32()
-    check(load().rt_nw_scene_obj_stage(s._h, str(path).encode(), kind, float(aspect), C.byref(cam), C.byref(n)),
-          "rt_nw_scene_obj_stage")
+    if not (smooth or gen_normals) and texture is None:
+        check(load().rt_nw_scene_obj_stage(s._h, str(path).encode(), kind, float(aspect), C.byref(cam), C.byref(n)),
+              "rt_nw_scene_obj_stage")
+        return s, cam, n.value
+    if texture is not None:
+        a = np.ascontiguousarray(texture, np.uint8)
+        ptr, ih, iw = a.ctypes.data_as(_u8), a.shape[0], a.shape[1]
+    else:
+        ptr, ih, iw = None, 0, 0
+    check(load().rt_nw_scene_obj_stage_attr(s._h, str(path).encode(), kind, _mesh_flags(smooth, texture is not None, gen_normals),
+                                            ptr, iw, ih, float(aspect), C.byref(cam), C.byref(n)),
+          "rt_nw_scene_obj_stage_attr")
     return s, cam, n.value
 
 
@@ -301,6 +355,22 @@ class NwRenderer:
                                       idx.ctypes.data_as(_ip), t.ctypes.data_as(_fp), face.ctypes.data_as(_ip)),
               "rt_nw_debug_hits")
         return idx, t, face
+
+    def debug_records(self, rays, keys=None):
+        """The hit record of each ray (rows o.xyz, d.xyz, time) as a render
+        makes it (rt_nw_debug_records): (insertion index or -1, t, rows p.xyz
+        n.xyz u v, material)."""
+        n = len(rays)
+        r = np.zeros((n, 8), np.float32)
+        r[:, :7] = np.asarray(rays)[:, :7]
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        idx, t = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        rec, mat = np.zeros((n, 8), np.float32), np.zeros(n, np.int32)
+        check(load().rt_nw_debug_records(self._h, r.ctypes.data_as(_fp),
+                                         None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                         idx.ctypes.data_as(_ip), t.ctypes.data_as(_fp), rec.ctypes.data_as(_fp),
+                                         mat.ctypes.data_as(_ip)), "rt_nw_debug_records")
+        return idx, t, rec, mat
 
     def last_segments(self):
         v = C.c_uint64()

@@ -108,6 +108,43 @@ int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, int32_t *n_tri
  * Errors as rt_nw_load_obj. */
 int rt_nw_scene_obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, double aspect, rt_nw_camera *cam,
                           int32_t *n_tris);
+/* ---- meshes with per-corner attributes: smooth shading and texture coordinates
+ * (DESIGN.md §9 "Triangles").  The calls above stay flat-shaded with the
+ * barycentric u, v and never look at vt or a corner's t. */
+enum { RT_NW_MESH_SMOOTH = 1, RT_NW_MESH_UV = 2, RT_NW_MESH_GEN_NORMALS = 4 };
+/* rt_nw_mesh with attributes; flags == 0 and uvs == NULL: rt_nw_mesh exactly.
+ * The winding is fixed from the normals as in rt_nw_mesh; when v1 and v2 are
+ * exchanged, their normals and uvs go with them.
+ * RT_NW_MESH_SMOOTH: a triangle all of whose corners have a normal is shaded
+ *   with the normals interpolated (each normalised in double, rounded to
+ *   float; how the renderer uses them: DESIGN.md §9); a triangle lacking one
+ *   stays flat.  An explicit corner normal not finite as a float or of zero
+ *   length: RT_EINVAL.
+ * RT_NW_MESH_GEN_NORMALS (with SMOOTH): a corner without a normal (normals ==
+ *   NULL here; an OBJ corner without n) takes the normalised sum, over every
+ *   triangle of this call using the same vertex index, of cross(v1 - v0, v2 -
+ *   v0) — in double, from the vertices as given, so area-weighted.  A
+ *   triangle with a vertex whose sum is zero or not finite stays flat.
+ * RT_NW_MESH_UV: uvs holds n_uvs (u, v) pairs, uv_idx three indices per
+ *   triangle (NULL: the vertex indices); a triangle's texture u, v are then
+ *   the interpolated pair instead of its barycentric weights, passed to the
+ *   texture unwrapped (an image texture clamps to [0, 1]).  An index out of
+ *   range, a value not finite as a float, or UV without uvs: RT_EINVAL. */
+int rt_nw_mesh_attr(rt_nw_scene *s, const double *verts, int32_t n_verts, const int32_t *tri_idx, int32_t n_tris,
+                    const double *normals, int32_t n_normals, const int32_t *normal_idx, const double *uvs,
+                    int32_t n_uvs, const int32_t *uv_idx, uint32_t flags, int32_t mat);
+/* rt_nw_load_obj under flags.  SMOOTH uses the file's vn (GEN_NORMALS: fills
+ * in the corners without one).  UV reads `vt u [v [w]]` (v defaults to 0, w is
+ * ignored) and the t of a corner (negative: counting back from the latest vt):
+ * a malformed vt, or a t of 0 or out of range, is RT_EINVAL with the line
+ * number; a face with a corner lacking t gets no uvs and keeps its
+ * barycentric u, v.  Without UV, vt lines and t are ignored as by rt_nw_load_obj. */
+int rt_nw_load_obj_attr(rt_nw_scene *s, const char *path, int32_t mat, uint32_t flags, int32_t *n_tris);
+/* rt_nw_scene_obj_stage with the mesh loaded under flags; rgb (w * h * 3 bytes
+ * as rt_nw_tex_image, may be NULL) becomes the texture of the mesh's
+ * lambertian or metal material (with RT_NW_DIELECTRIC: RT_EINVAL). */
+int rt_nw_scene_obj_stage_attr(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
+                               int32_t w, int32_t h, double aspect, rt_nw_camera *cam, int32_t *n_tris);
 /* constant_medium(boundary, density, tex) constant_medium.h: boundary is a
  * sphere, moving sphere or box object, optionally under translate/rotate_y
  * (a rectangle, a triangle or a set of objects: RT_EUNSUPPORTED). */
@@ -167,6 +204,12 @@ typedef struct rt_nw_flat {
   float background[3];
 } rt_nw_flat;
 int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out);
+/* The triangle attribute records beside rt_nw_scene_flat (same lifetime):
+ *   attr        : n_attr * 16 floats: the unit normals of v0, v1, v2 (9), their
+ *                 uvs (6), flags as int32 bits (bit 0 normals, bit 1 uvs; the
+ *                 absent part is zero)
+ *   attr_of_obj : per flattened object its record index, or -1 */
+int rt_nw_scene_flat_attr(rt_nw_scene *s, int32_t *n_attr, const float **attr, const int32_t **attr_of_obj);
 /* Host only (no device needed): the uniform grid rt_nw_ctx_set_scene would
  * build for this scene — cells per axis (zeros: no grid),
  * the fullest cell's object count, the brute-force list's length and the
@@ -218,6 +261,13 @@ int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_
  * and the box face (-1: none), as one segment of rt_nw_debug_trace. */
 int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id, float *out_t,
                      int32_t *out_face);
+/* Validation: the hit record of n given rays — the closest hit as
+ * rt_nw_debug_hits resolves it, then the record a render makes of it.  Out per
+ * ray: the winner's insertion index, t, out_pnuv = {p.xyz, n.xyz, u, v} (world
+ * space; u, v are 0 unless the material's texture reads them) and the
+ * material; a miss writes index -1 and zeros. */
+int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id, float *out_t,
+                        float *out_pnuv /* 8 floats per ray */, int32_t *out_mat);
 /* world.hit calls of the last render (waits for it). */
 int rt_nw_ctx_last_segments(rt_nw_ctx *ctx, uint64_t *segments);
 /* Diagnostic: the kernel of the last render, {persistent, uniform grid,
