@@ -138,6 +138,10 @@ SIGNATURES = {
     "rt_nw_scene_obj_stage_attr": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
                                              C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
     "rt_nw_scene_flat_attr": (C.c_int, [C.c_void_p, _ip, C.POINTER(_fp), C.POINTER(_ip)]),
+    "rt_nw_scene_obj_stage_copies": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
+    "rt_nw_shared": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rt_nw_scene_instancing_stats": (C.c_int, [C.c_void_p, _ip]),
     "rt_nw_debug_records": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _fp, _ip]),
     "rt_nw_constant_medium": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     "rt_nw_medium_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

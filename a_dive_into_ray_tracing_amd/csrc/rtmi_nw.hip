@@ -88,6 +88,19 @@ template <bool S> constexpr int persist_waves() { return S ? RTMI_NW_SIMPLE_WAVE
 // for two blocks per CU, and for one (160 KB LDS per CU).  The launch path
 // also checks the kernel's actual static size (hipFuncGetAttributes), so a
 // new __shared__ variable cannot silently push a block past the CU.
+// Scenes with placements of shared meshes (TRI = 3, the two-level walk
+// hit_world_nw_inst): minimum waves per SIMD of its persistent instantiations.
+// The walk keeps the local ray, its inverses and the triangle constants beside
+// the world ray's: 128 VGPRs without scratch at 4 waves per SIMD (one 16-wave
+// block per CU), 64 VGPRs with ~185 spilled at 8 (two blocks).  The bottom
+// level is a chain of dependent global loads, and the waves that hide them win
+// once the meshes are large: a 16 x 16 field of an 81 920-triangle mesh at 800
+// x 800 x 64 renders in 157.5 ms at 4 and 123.7 ms at 8, of a 5 120-triangle
+// one in 81.8 and 74.6; only the 4 x 4 field of the small mesh prefers 4 (49.0
+// against 50.1).  profiles/instancing/README.md
+#ifndef RTMI_NW_INST_PER_EU
+#define RTMI_NW_INST_PER_EU 8
+#endif
 constexpr size_t kCuLds = 160 * 1024;
 constexpr size_t kPStaticLds = (sizeof(unsigned long long) * 3 * 64 * kPWaves + 23 * sizeof(float) + 255) / 256 * 256;
 constexpr size_t kPTwoBlockBudget = kCuLds / 2 - kPStaticLds;
@@ -253,8 +266,10 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
       const uint64_t seg_key = !S && sc.has_media ? rng.next() : 0ull;
       float t;
       int face;
-      const int32_t k = GRID ? hit_world_nw_grid<S, TRI>(sc, o, d, time, seg_key, t, face, &cnt)
-                             : hit_world_nw<LDS_NODES, LDS_OBJS, TRI>(sc, o, d, time, seg_key, t, face, &cnt);
+      int32_t sub = -1;  // the winner's pool slot when it is a placement's triangle (TRI = 3)
+      const int32_t k = TRI == 3 ? hit_world_nw_inst<LDS_NODES, LDS_OBJS>(sc, o, d, time, seg_key, t, face, sub, &cnt)
+                        : GRID   ? hit_world_nw_grid<S, TRI>(sc, o, d, time, seg_key, t, face, &cnt)
+                                 : hit_world_nw<LDS_NODES, LDS_OBJS, TRI>(sc, o, d, time, seg_key, t, face, &cnt);
 #if RTMI_NW_PHASES
       pb = __builtin_amdgcn_s_memtime();
 #endif
@@ -262,8 +277,9 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
         col = mk(T.x * sc.bg[0], T.y * sc.bg[1], T.z * sc.bg[2]);
         done = true;
       } else {
-        const Rec rec = S || k < sc.nobj ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face, attr_view_of(sc), k)
-                                         : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
+        const Rec rec = TRI == 3 && k < sc.nobj ? make_rec_inst(sc, k, sub, o, d, time, t, face)
+                        : S || k < sc.nobj      ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face, attr_view_of(sc), k)
+                                                : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
         const Mat m = sc.mat[rec.mat];
         V at, nd;
         if (m.kind == kDiffuseLight) {  // emitted, no scatter: main.cu:76-90
@@ -339,7 +355,8 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
 }
 
 // TRI (last parameter of both kernels): the scene holds no triangle (0), triangles (1), triangles with
-// attribute records (2; hit_object, make_rec)
+// attribute records (2; hit_object, make_rec), placements of shared meshes (3; hit_world_nw_inst: BVH
+// shapes only, such a scene has no uniform grid)
 template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, int TRI = 0>
 __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, unsigned long long *__restrict__ accum,
                                                              float *__restrict__ out,
@@ -362,7 +379,7 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
 template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
-__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : RTMI_NW_PERSIST_PER_EU)) void render_persistent(View sc, Args a,
+__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
                                                                   unsigned long long *__restrict__ segments,
@@ -388,7 +405,10 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
 // i, j, sample s): per segment o.xyz, d.xyz, t, winner insertion index (as
 // float bits) — the oracle's or_nw_trace records the same.
 // has_attr: the scene has triangle attribute records (attr_view_of).
-__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
+// INST: a scene with placements of shared meshes (the two-level walk).
+template <bool INST>
+__device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i, int j, int s, float *rec, int cap, int *n_out,
+                                           int has_attr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const AttrView av = has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr};
   Xoro rng;
@@ -406,14 +426,18 @@ __global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, i
     const uint64_t seg_key = sc.has_media ? rng.next() : 0ull;
     float t;
     int face;
-    const int32_t k = hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
+    int32_t sub = -1;
+    const int32_t k = INST ? hit_world_nw_inst<false, false>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
+                           : hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
-    r[7] = __int_as_float(k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj]);
+    r[7] = __int_as_float(k < 0 ? -1 : k < sc.nobj ? (INST ? inst_winner_id(sc, k, sub) : sc.obj_id[k]) : sc.med_id[k - sc.nobj]);
     r[8] = r[9] = r[10] = 0.f;
     r[11] = __int_as_float(face);
     if (k < 0) break;
-    const Rec rc = k < sc.nobj ? make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
+    const Rec rc = k >= sc.nobj ? make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time)
+                   : INST       ? make_rec_inst(sc, k, sub, o, d, time, t, face)
+                                : make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
     V at, nd;
@@ -422,6 +446,12 @@ __global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, i
     d = nd;
   }
   *n_out = n;
+}
+__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
+  trace_body<false>(sc, a, i, j, s, rec, cap, n_out, has_attr);
+}
+__global__ void trace_inst_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
+  trace_body<true>(sc, a, i, j, s, rec, cap, n_out, 0);
 }
 
 __global__ void finalize_kernel(const unsigned long long *__restrict__ acc, float *__restrict__ out, size_t n) {
@@ -449,6 +479,25 @@ __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *_
   const int32_t k = GRID ? hit_world_nw_grid<false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
                          : hit_world_nw<false, false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
   out_id[i] = k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
+  out_t[i] = t;
+  out_face[i] = face;
+}
+// ... of a scene with placements of shared meshes: the two-level walk, nodes
+// and records in global memory
+__global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const float *__restrict__ rays,
+                                                              const unsigned long long *__restrict__ keys, int32_t n,
+                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                              int32_t *__restrict__ out_face) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *r = rays + 8 * size_t(i);
+  const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
+  NwCount cnt{0, 0, 0, 0};
+  float t;
+  int face;
+  int32_t sub;
+  const int32_t k = hit_world_nw_inst<false, false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
+  out_id[i] = k < 0 ? -1 : k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_face[i] = face;
 }
@@ -486,6 +535,36 @@ __global__ __launch_bounds__(256) void debug_records_kernel(View sc, const float
   const Rec rc = k < sc.nobj ? make_rec<false, 2>(sc, sc.obj[k], o, d, r[6], t, face, av, k)
                              : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
   out_id[i] = k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
+  out_t[i] = t;
+  out_mat[i] = rc.mat;
+  q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
+  q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
+  q[6] = rc.u; q[7] = rc.v;
+}
+// ... of a scene with placements of shared meshes (as debug_hits_inst_kernel)
+__global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const float *__restrict__ rays,
+                                                                 const unsigned long long *__restrict__ keys, int32_t n,
+                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *r = rays + 8 * size_t(i);
+  const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
+  NwCount cnt{0, 0, 0, 0};
+  float t;
+  int face;
+  int32_t sub;
+  const int32_t k = hit_world_nw_inst<false, false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
+  float *q = out_pnuv + 8 * size_t(i);
+  if (k < 0) {
+    out_id[i] = -1;
+    out_t[i] = 0.0f;
+    out_mat[i] = 0;
+    for (int c = 0; c < 8; ++c) q[c] = 0.0f;
+    return;
+  }
+  const Rec rc = k < sc.nobj ? make_rec_inst(sc, k, sub, o, d, r[6], t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
+  out_id[i] = k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_mat[i] = rc.mat;
   q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
@@ -535,7 +614,9 @@ struct rt_nw_ctx {
   int32_t accel = RT_NW_ACCEL_AUTO;
   float bg[3] = {0.f, 0.f, 0.f};
   int32_t has_media = 0;
-  int32_t has_tri = 0;  // the kernels' TRI: 0 no triangle, 1 triangles, 2 triangles with attribute records
+  int32_t has_tri = 0;  // the kernels' TRI: 0 no triangle, 1 triangles, 2 triangles with attribute records,
+                        // 3 placements of shared meshes (nobj, nnodes: the top level's)
+  int32_t npool = 0, nbot = 0;  // TRI = 3: pool slots behind obj[nobj], bottom-level nodes behind nodes[2 * nnodes]
   int32_t nattr = 0;    // attribute records behind obj[nobj] (their locator behind obj_id[nobj]); 0: neither exists
   unsigned long long *accum = nullptr;
   size_t accum_cap = 0;
@@ -689,10 +770,60 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   // every index the kernel follows is checked here, once
   const int32_t nt = int32_t(ds.tex.size()), nm = int32_t(ds.mat.size()), ni = int32_t(ds.inst.size());
   const int32_t np = int32_t(ds.perlin_perm.size() / (3 * kPerlinN)), nim = int32_t(ds.image.size());
+  const bool two_level = !ds.place_mesh.empty();
   for (const Obj &o : ds.obj)
-    if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere || (o.kind > kBox && o.kind != kTriangle) || o.aux < 0 ||
-        o.aux > int32_t(ds.med.size()))
+    if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere ||
+        (o.kind > kBox && o.kind != kTriangle && !(two_level && o.kind == kInstance)) || o.aux < 0 || o.aux > int32_t(ds.med.size()))
       return set_error(RT_EINVAL, "rt_nw: object with bad material/instance/kind");
+  // shared meshes: every link the two-level walk follows (rtmi_nw_path.h hit_world_nw_inst)
+  const size_t npool = ds.pool.size(), nbot = ds.bnodes.size();
+  if (!two_level && (npool || nbot || !ds.mesh.empty())) return set_error(RT_EINVAL, "rt_nw: shared pool without a placement");
+  if (two_level) {
+    if (ds.pool_j.size() != npool || ds.place_slot.size() != ds.place_mesh.size())
+      return set_error(RT_EINVAL, "rt_nw: shared mesh tables do not match");
+    for (const Obj &o : ds.pool)
+      if (o.kind != kTriangle || o.mat < 0 || o.mat >= nm || o.inst != -1 || o.aux != 0)
+        return set_error(RT_EINVAL, "rt_nw: bad record in a shared pool");
+    for (const DeviceScene::SharedMesh &M : ds.mesh) {
+      if (M.node0 < 0 || M.n_nodes < 0 || size_t(M.node0) + size_t(M.n_nodes) > nbot || M.pool0 < 0 || M.n_pool < 0 ||
+          size_t(M.pool0) + size_t(M.n_pool) > npool || (M.n_pool > 0) != (M.n_nodes > 0))
+        return set_error(RT_EINVAL, "rt_nw: shared mesh out of range");
+      for (int32_t i = M.node0; i < M.node0 + M.n_nodes; ++i) {
+        const Node &nd = ds.bnodes[size_t(i)];
+        const int32_t first = nd.leaf >> 4, cnt = nd.leaf & 15;
+        if (nd.skip <= i || nd.skip > M.node0 + M.n_nodes ||
+            (nd.leaf >= 0 && (cnt < 1 || first < M.pool0 || first + cnt > M.pool0 + M.n_pool)))
+          return set_error(RT_EINVAL, "rt_nw: bottom-level link out of its mesh");
+      }
+      for (int32_t q = M.pool0; q < M.pool0 + M.n_pool; ++q)
+        if (ds.pool_j[size_t(q)] < 0 || ds.pool_j[size_t(q)] >= M.n_tris) return set_error(RT_EINVAL, "rt_nw: bad triangle number in a shared pool");
+    }
+    size_t n_records = 0;
+    for (size_t k = 0; k < ds.obj.size(); ++k) n_records += ds.obj[k].kind == kInstance;
+    size_t n_slots = 0;
+    for (size_t p = 0; p < ds.place_mesh.size(); ++p) {
+      const int32_t k = ds.place_slot[p], mi = ds.place_mesh[p];
+      if (mi < 0 || size_t(mi) >= ds.mesh.size()) return set_error(RT_EINVAL, "rt_nw: placement of an unknown mesh");
+      if (k < 0) continue;  // (a mesh without a triangle that can be hit)
+      ++n_slots;
+      const DeviceScene::SharedMesh &M = ds.mesh[size_t(mi)];
+      int32_t w[4], np;
+      if (size_t(k) >= ds.obj.size() || ds.obj[size_t(k)].kind != kInstance) return set_error(RT_EINVAL, "rt_nw: placement without its record");
+      std::memcpy(w, ds.obj[size_t(k)].g0, sizeof w);
+      std::memcpy(&np, &ds.obj[size_t(k)].g1[0], 4);
+      if (w[0] != M.node0 || w[1] != M.node0 + M.n_nodes || w[2] != M.pool0 || np != M.n_pool || M.n_nodes < 1 || w[3] < 0 ||
+          int64_t(w[3]) + M.n_tris > (int64_t(1) << 27))
+        return set_error(RT_EINVAL, "rt_nw: placement record does not match its mesh");
+    }
+    if (n_slots != n_records) return set_error(RT_EINVAL, "rt_nw: placement records do not match the placements");
+    for (const Node &nd : ds.nodes) {  // a placement is alone in its leaf
+      if (nd.leaf < 0) continue;
+      const int32_t first = nd.leaf >> 4, cnt = nd.leaf & 15;
+      if (first < 0 || size_t(first) + size_t(cnt) > ds.obj.size()) return set_error(RT_EINVAL, "rt_nw: leaf out of range");
+      for (int32_t k = first; k < first + cnt; ++k)
+        if (ds.obj[size_t(k)].kind == kInstance && cnt != 1) return set_error(RT_EINVAL, "rt_nw: placement shares a leaf");
+    }
+  }
   for (const Obj &o : ds.med) {
     const int bk = o.aux & 255, ns = o.aux >> 8;
     if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind != kMedium || (bk != kSphere && bk != kMovingSphere && bk != kBox) ||
@@ -707,7 +838,8 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
     if (t.kind == kImage && (t.a < 0 || t.a >= nim)) return set_error(RT_EINVAL, "rt_nw: bad image index");
   }
   // nodes as lo[] = {bmin, skip} and hi[] = {bmax, leaf} (two independent loads)
-  std::vector<float4> split(2 * ds.nodes.size());
+  // ... then the bottom-level nodes of shared meshes, as {lo, hi} pairs
+  std::vector<float4> split(2 * ds.nodes.size() + 2 * nbot);
   for (size_t i = 0; i < ds.nodes.size(); ++i) {
     const Node &nd = ds.nodes[i];
     float sk, lf;
@@ -716,6 +848,14 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
     split[i] = make_float4(nd.bmin[0], nd.bmin[1], nd.bmin[2], sk);
     split[ds.nodes.size() + i] = make_float4(nd.bmax[0], nd.bmax[1], nd.bmax[2], lf);
   }
+  for (size_t i = 0; i < nbot; ++i) {
+    const Node &nd = ds.bnodes[i];
+    float sk, lf;
+    std::memcpy(&sk, &nd.skip, 4);
+    std::memcpy(&lf, &nd.leaf, 4);
+    split[2 * ds.nodes.size() + 2 * i] = make_float4(nd.bmin[0], nd.bmin[1], nd.bmin[2], sk);
+    split[2 * ds.nodes.size() + 2 * i + 1] = make_float4(nd.bmax[0], nd.bmax[1], nd.bmax[2], lf);
+  }
   // attribute records: the locator holds one entry per object, -1 or a record of a triangle
   const size_t nattr = ds.obj_attr.empty() ? 0 : ds.attr.size();
   if (!ds.obj_attr.empty() && (ds.obj_attr.size() != ds.obj.size() || nattr == 0))
@@ -723,15 +863,29 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   for (size_t i = 0; i < ds.obj_attr.size(); ++i)
     if (ds.obj_attr[i] < -1 || ds.obj_attr[i] >= int32_t(nattr) || (ds.obj_attr[i] >= 0 && ds.obj[i].kind != kTriangle))
       return set_error(RT_EINVAL, "rt_nw: attribute record index out of range");
+  if (ds.pool_attr.size() != (nattr ? npool : 0)) return set_error(RT_EINVAL, "rt_nw: attribute locator does not match the shared pool");
+  for (int32_t a : ds.pool_attr)
+    if (a < -1 || a >= int32_t(nattr)) return set_error(RT_EINVAL, "rt_nw: attribute record index out of range");
   // the records follow the objects in one allocation and the locator follows
   // the insertion indices (rtmi_nw_path.h attr_view_of): 64 B records behind
   // 48 B ones, so the tail is sized in DevObj units
-  std::vector<DevObj> dobj(ds.obj.size() + (nattr * sizeof(TriAttr) + sizeof(DevObj) - 1) / sizeof(DevObj));
-  if (nattr) std::memcpy(static_cast<void *>(dobj.data() + ds.obj.size()), ds.attr.data(), nattr * sizeof(TriAttr));
+  // With placements (rtmi_nw_path.h pool_view_of): the pool between the
+  // objects and the records; behind the insertion indices {pool slots,
+  // attribute records}, the pool's triangle numbers, then the locator over
+  // objects and pool slots.
+  const size_t nrec = ds.obj.size() + npool;
+  std::vector<DevObj> dobj(nrec + (nattr * sizeof(TriAttr) + sizeof(DevObj) - 1) / sizeof(DevObj));
+  if (nattr) std::memcpy(static_cast<void *>(dobj.data() + nrec), ds.attr.data(), nattr * sizeof(TriAttr));
   std::vector<int32_t> dobj_id = ds.obj_id;
+  if (two_level) {
+    dobj_id.push_back(int32_t(npool));
+    dobj_id.push_back(int32_t(nattr));
+    dobj_id.insert(dobj_id.end(), ds.pool_j.begin(), ds.pool_j.end());
+  }
   if (nattr) dobj_id.insert(dobj_id.end(), ds.obj_attr.begin(), ds.obj_attr.end());
-  for (size_t i = 0; i < ds.obj.size(); ++i) {
-    const Obj &o = ds.obj[i];
+  if (nattr) dobj_id.insert(dobj_id.end(), ds.pool_attr.begin(), ds.pool_attr.end());
+  for (size_t i = 0; i < nrec; ++i) {
+    const Obj &o = i < ds.obj.size() ? ds.obj[i] : ds.pool[i - ds.obj.size()];
     DevObj &q = dobj[i];
     for (int c = 0; c < 4; ++c) {
       q.g0[c] = o.g0[c];
@@ -753,7 +907,7 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   Guard g(ctx->device);
   // the context's structures are replaced below: until that completes, no
   // render may use a mix of old counts and new buffers
-  ctx->nobj = ctx->nmed = ctx->nnodes = ctx->nattr = 0;
+  ctx->nobj = ctx->nmed = ctx->nnodes = ctx->nattr = ctx->npool = ctx->nbot = 0;
   ctx->grid_ok = false;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   int rc;
@@ -806,6 +960,9 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   for (const Obj &o : ds.obj) ctx->has_tri |= o.kind == kTriangle ? 1 : 0;
   ctx->nattr = int32_t(nattr);
   if (nattr) ctx->has_tri = 2;
+  if (two_level) ctx->has_tri = 3;
+  ctx->npool = int32_t(npool);
+  ctx->nbot = int32_t(nbot);
   bool simple = ds.med.empty();
   for (const Obj &o : ds.obj) simple = simple && o.inst < 0 && (o.kind == kSphere || o.kind == kMovingSphere);
   for (const Tex &t : ds.tex)
@@ -919,9 +1076,11 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   const View v = view_of(ctx);
   // objects staged beside the nodes only when two blocks still fit a CU (or
   // when one block per CU is all the nodes allow anyway)
+  // (the two-level kernels below 8 waves per SIMD run one block per CU whatever they stage)
+  const bool one_block = ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8;
   const bool p_objs = RTMI_NW_LDS_OBJS && persist &&
                       (node_bytes + obj_bytes <= kPTwoBlockBudget ||
-                       (node_bytes > kPTwoBlockBudget && node_bytes + obj_bytes <= kPLdsBudget));
+                       ((one_block || node_bytes > kPTwoBlockBudget) && node_bytes + obj_bytes <= kPLdsBudget));
   const bool g_grid = use_grid && !persist && gbytes <= kLdsBudget;  // grid kernel with the grid staged per block
   if (use_grid && !persist && !g_grid) return set_error(RT_EINVAL, "rt_nw: grid does not fit the grid kernel's LDS");
   const bool lds_nodes = !persist && !use_grid && ctx->nnodes > 0 && node_bytes <= kLdsBudget,
@@ -933,19 +1092,31 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   // (persistent) how many of its blocks stay resident with those bytes
   auto kernel_of = [&](auto tri) -> const void * {
     constexpr int T = decltype(tri)::value;
-    return simple                ? (const void *)render_persistent<true, true, true, true>
-           : persist && use_grid ? (const void *)render_persistent<true, true, true, false, T>
-           : persist && p_objs   ? (const void *)render_persistent<true, true, false, false, T>
-           : persist             ? (const void *)render_persistent<true, false, false, false, T>
-           : g_grid              ? (const void *)render_kernel<true, false, false, true, T>
-           : lds_objs            ? (const void *)render_kernel<true, true, true, false, T>
-           : lds_nodes           ? (const void *)render_kernel<true, true, false, false, T>
-                                 : (const void *)render_kernel<true, false, false, false, T>;
+    if constexpr (T == 3)  // (BVH shapes only)
+      return persist && p_objs ? (const void *)render_persistent<true, true, false, false, T>
+             : persist         ? (const void *)render_persistent<true, false, false, false, T>
+             : lds_objs        ? (const void *)render_kernel<true, true, true, false, T>
+             : lds_nodes       ? (const void *)render_kernel<true, true, false, false, T>
+                               : (const void *)render_kernel<true, false, false, false, T>;
+    else
+      return simple                ? (const void *)render_persistent<true, true, true, true>
+             : persist && use_grid ? (const void *)render_persistent<true, true, true, false, T>
+             : persist && p_objs   ? (const void *)render_persistent<true, true, false, false, T>
+             : persist             ? (const void *)render_persistent<true, false, false, false, T>
+             : g_grid              ? (const void *)render_kernel<true, false, false, true, T>
+             : lds_objs            ? (const void *)render_kernel<true, true, true, false, T>
+             : lds_nodes           ? (const void *)render_kernel<true, true, false, false, T>
+                                   : (const void *)render_kernel<true, false, false, false, T>;
   };
   using Tri0 = std::integral_constant<int, 0>;
   using Tri1 = std::integral_constant<int, 1>;
   using Tri2 = std::integral_constant<int, 2>;
-  const void *kfn = ctx->has_tri == 2 ? kernel_of(Tri2{}) : ctx->has_tri ? kernel_of(Tri1{}) : kernel_of(Tri0{});
+  using Tri3 = std::integral_constant<int, 3>;
+  if (ctx->has_tri == 3 && use_grid) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
+  const void *kfn = ctx->has_tri == 3   ? kernel_of(Tri3{})
+                    : ctx->has_tri == 2 ? kernel_of(Tri2{})
+                    : ctx->has_tri      ? kernel_of(Tri1{})
+                                        : kernel_of(Tri0{});
   {
     hipFuncAttributes fa;
     HIP_TRY(hipFuncGetAttributes(&fa, kfn));
@@ -988,16 +1159,24 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   auto launch_t = [&](auto chunked, auto tri) {
     constexpr bool C = decltype(chunked)::value;
     constexpr int T = decltype(tri)::value;
-    if (simple)
-      hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
-    else if (persist && use_grid)
-      hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
-    else if (persist && p_objs)
+    if constexpr (T != 3) {  // (a scene with placements has no grid)
+      if (simple) {
+        hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+        return;
+      }
+      if (persist && use_grid) {
+        hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+        return;
+      }
+      if (!persist && g_grid) {
+        hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+        return;
+      }
+    }
+    if (persist && p_objs)
       hipLaunchKernelGGL((render_persistent<C, true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
     else if (persist)
       hipLaunchKernelGGL((render_persistent<C, false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
-    else if (g_grid)
-      hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
     else if (lds_objs)
       hipLaunchKernelGGL((render_kernel<C, true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
     else if (lds_nodes)
@@ -1006,7 +1185,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
       hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
   };
   auto launch = [&](auto chunked) {
-    if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
+    if (ctx->has_tri == 3) launch_t(chunked, Tri3{});
+    else if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
     else if (ctx->has_tri) launch_t(chunked, Tri1{});
     else launch_t(chunked, Tri0{});
   };
@@ -1062,8 +1242,11 @@ RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   int *d_n = nullptr;
   HIP_TRY(hipMalloc(&d_rec, size_t(cap) * 12 * sizeof(float)));
   HIP_TRY(hipMalloc(&d_n, sizeof(int)));
-  hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n,
-                     ctx->nattr > 0 ? 1 : 0);
+  if (ctx->has_tri == 3)
+    hipLaunchKernelGGL(trace_inst_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
+  else
+    hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n,
+                       ctx->nattr > 0 ? 1 : 0);
   hipError_t e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(n, d_n, sizeof(int), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(rec, d_rec, size_t(*n) * 12 * sizeof(float), hipMemcpyDeviceToHost);
@@ -1095,7 +1278,9 @@ RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64
   if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
-    if (grid)
+    if (ctx->has_tri == 3)
+      hipLaunchKernelGGL(debug_hits_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
+    else if (grid)
       hipLaunchKernelGGL(debug_hits_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id,
                          d_t, d_face);
     else
@@ -1140,7 +1325,10 @@ RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uin
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
     const int has_attr = ctx->nattr > 0 ? 1 : 0;
-    if (grid)
+    if (ctx->has_tri == 3)
+      hipLaunchKernelGGL(debug_records_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
+                         d_mat);
+    else if (grid)
       hipLaunchKernelGGL(debug_records_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, has_attr,
                          d_id, d_t, d_rec, d_mat);
     else

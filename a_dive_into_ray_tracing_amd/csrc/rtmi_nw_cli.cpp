@@ -8,7 +8,7 @@
 //                  [--spp S] [--depth D] [--seed N] [--texture FILE.ppm]
 //                  [--out FILE|-] [--p6] [--rtl]
 //   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
-//                  [--obj-texture FILE.ppm] [--width W] ...
+//                  [--obj-texture FILE.ppm] [--obj-copies N] [--width W] ...
 //
 // --obj (exclusive with --scene) renders a Wavefront OBJ mesh
 // (rt_nw_scene_obj_stage): scaled and centred into the box [-1, 1] x [0, 2] x
@@ -18,6 +18,8 @@
 // (--obj-gen-normals: area-weighted vertex normals where the file has none),
 // --obj-texture maps a binary PPM (P6, read as --texture is) onto the mesh by
 // the file's vt (lambertian or metal); none of the three is valid with --scene.
+// --obj-copies N stages the model as one shared mesh (rt_nw_shared) placed
+// N x N times on the ground (rt_nw_scene_obj_stage_copies; 1: the stage above).
 //
 // --texture is the earth image as a binary PPM (P6; the reference decodes
 // earthmap.jpeg with stb_image, main.cu:497-510 — convert it once, e.g. with
@@ -73,7 +75,8 @@ static bool read_p6(const char *path, std::vector<uint8_t> &px, int &w, int &h) 
 int main(int argc, char **argv) {
   std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
-  int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0;
+  int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
+  bool copies_given = false;
   unsigned long long seed = 1984;
   for (int a = 1; a < argc; a++) {
     auto need = [&](const char *f) -> const char * {
@@ -86,6 +89,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--obj-smooth")) obj_smooth = true;
     else if (!std::strcmp(argv[a], "--obj-gen-normals")) obj_gen = true;
     else if (!std::strcmp(argv[a], "--obj-texture")) obj_texture = need("--obj-texture");
+    else if (!std::strcmp(argv[a], "--obj-copies")) { obj_copies = std::atoi(need("--obj-copies")); copies_given = true; }
     else if (!std::strcmp(argv[a], "--width")) W = std::atoi(need("--width"));
     else if (!std::strcmp(argv[a], "--height")) H = std::atoi(need("--height"));
     else if (!std::strcmp(argv[a], "--spp")) spp = std::atoi(need("--spp"));
@@ -99,12 +103,14 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
                            "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
                            "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]\n"
-                           "          [--obj-texture FILE.ppm] [--width W] [--height H] ...\n"
+                           "          [--obj-texture FILE.ppm] [--obj-copies N] [--width W] [--height H] ...\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
                            "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
                            "  --obj-smooth: interpolated vn (--obj-gen-normals: generated where missing);\n"
-                           "  --obj-texture: a P6 image mapped by vt (lambertian, metal); all three need --obj\n",
+                           "  --obj-texture: a P6 image mapped by vt (lambertian, metal); all three need --obj\n"
+                           "  --obj-copies N (1..256, needs --obj): the model as one shared mesh placed N x N times, 3 units\n"
+                           "         apart, each copy turned and nudged by a fixed formula; the camera backs away with N\n",
                    argv[0], argv[0]);
       return 2;
     }
@@ -117,6 +123,10 @@ int main(int argc, char **argv) {
   if (!obj.empty() && scene_given) { std::fprintf(stderr, "--scene and --obj are exclusive\n"); return 2; }
   if (obj.empty() && (obj_smooth || obj_gen || !obj_texture.empty())) {
     std::fprintf(stderr, "--obj-smooth, --obj-gen-normals and --obj-texture need --obj (not valid with --scene)\n");
+    return 2;
+  }
+  if (copies_given && (obj.empty() || obj_copies < 1 || obj_copies > 256)) {
+    std::fprintf(stderr, "--obj-copies needs --obj and a count in 1..256\n");
     return 2;
   }
   const int obj_kind = obj_mat == "lambertian" ? RT_NW_LAMBERTIAN : obj_mat == "metal" ? RT_NW_METAL : obj_mat == "glass" ? RT_NW_DIELECTRIC : -1;
@@ -145,7 +155,11 @@ int main(int argc, char **argv) {
   if ((rc = rt_nw_scene_create(&s))) return die("rt_nw_scene_create", rc);
   if (!obj.empty()) {
     const uint32_t flags = (obj_smooth ? RT_NW_MESH_SMOOTH : 0) | (obj_gen ? RT_NW_MESH_GEN_NORMALS : 0) | (oimg.empty() ? 0 : RT_NW_MESH_UV);
-    if (!flags) {
+    if (obj_copies > 1) {
+      if ((rc = rt_nw_scene_obj_stage_copies(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh, obj_copies,
+                                             double(W) / H, &cam, nullptr)))
+        return die("rt_nw_scene_obj_stage_copies", rc);
+    } else if (!flags) {
       if ((rc = rt_nw_scene_obj_stage(s, obj.c_str(), obj_kind, double(W) / H, &cam, nullptr))) return die("rt_nw_scene_obj_stage", rc);
     } else if ((rc = rt_nw_scene_obj_stage_attr(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh,
                                                 double(W) / H, &cam, nullptr))) {

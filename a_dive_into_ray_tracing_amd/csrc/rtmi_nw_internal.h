@@ -48,10 +48,30 @@ struct DeviceScene {
   std::vector<uint16_t> grid_cell_start;   // ncells + 1
   std::vector<uint16_t> grid_refs;         // object indices (leaf order) per cell
   std::vector<int32_t> grid_big;           // objects tested brute force beside the grid (leaf order)
+  // Shared meshes (rt_nw_shared, DESIGN.md §9 "Shared meshes"); all empty in a
+  // scene without a placement.  Each placement is one kInstance record in obj
+  // (alone in its top-level leaf; obj_id = first(p)); the triangles of every
+  // placed mesh sit once in the pool, in the leaf order of that mesh's
+  // bottom-level BVH.  bnodes' skip links and leaf ranges are absolute: indices
+  // into bnodes and into pool, each inside its mesh's ranges.
+  struct SharedMesh {
+    int32_t node0, n_nodes;  // its bottom-level BVH in bnodes
+    int32_t pool0, n_pool;   // its triangles in pool
+    int32_t n_tris;          // triangles of its subtree in flatten order (collinear ones included)
+  };
+  std::vector<SharedMesh> mesh;      // placed meshes, in order of first placement
+  std::vector<int32_t> place_mesh;   // per placement, in insertion order: its mesh
+  std::vector<int32_t> place_slot;   // ... and its kInstance record in obj
+  std::vector<Obj> pool;             // triangles in local space, inst = -1
+  std::vector<int32_t> pool_j;       // pool slot -> index j in its mesh's flatten order (insertion index first(p) + j)
+  std::vector<int32_t> pool_attr;    // attribute record of a pool slot or -1; empty when obj_attr is
+  std::vector<Node> bnodes;          // the bottom-level BVHs, one after the other
 };
 
 // Flatten the world and build the BVH (RT_OK or RT_E*).
 int build_device_scene(rt_nw_scene *s, DeviceScene &out);
+// rt_nw_scene_instancing_stats: counts of build_device_scene, host only.
+int scene_instancing_stats(rt_nw_scene *s, int32_t out[6]);
 // rt_nw_scene_grid_stats: the grid of build_device_scene, host only.
 int scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *max_cell, int32_t *n_big, int32_t *n_refs);
 

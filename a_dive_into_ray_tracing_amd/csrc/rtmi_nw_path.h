@@ -483,7 +483,9 @@ __device__ __forceinline__ unsigned nw_test_flop(int kind, bool inst) {
 // and 2 are the same code).  Scenes without triangles run the TRI = 0
 // instantiations, the kernels as they were before triangles existed (the
 // triangle test inside the 64-VGPR BVH kernels cost the final scene 15%,
-// profiles/mesh/README.md).
+// profiles/mesh/README.md).  The kernels' TRI = 3 (a scene with placements of
+// shared meshes) is a walk of its own, hit_world_nw_inst below: it tests
+// top-level objects as TRI = 1 does and makes records as TRI = 2 does.
 // S: a spheres-only scene (rt_nw_ctx_set_scene's check: spheres and moving
 // spheres, no instances, no media, solid and checker textures): the other
 // kinds' code is compiled out — the same arithmetic for the kinds that remain.
@@ -998,6 +1000,205 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
   r.p = p;
   r.n = n;
   return r;
+}
+
+// ---------------------------------------------------------------------------
+// Shared meshes (rt_nw_shared; DESIGN.md §9 "Shared meshes"): the two-level
+// walk, TRI = 3.  A placement is one top-level record of kind kInstance, alone
+// in its leaf; the triangles of every placed mesh sit once in a pool, in the
+// leaf order of that mesh's bottom-level BVH, in the mesh's local space.
+// Where the tables live (View, and with it every kernel's argument block, is
+// what it was): the pool follows the sc.nobj top-level records in the objects'
+// allocation, the attribute records follow the pool; behind the top level's
+// insertion indices come two words {pool slots, attribute records}, the pool
+// slots' triangle numbers j (insertion index = the placement's first(p) + j)
+// and, when there are attribute records, the locator over top-level slots and
+// pool slots alike; the bottom-level nodes follow the top level's in the
+// nodes' allocation, as {bmin, skip}, {bmax, leaf} pairs with absolute links.
+// The pool and the bottom-level nodes are read from global memory.
+// Why the closest hit is the flattened scene's, bit for bit: a flattened copy
+// of triangle j under placement p is tested with to_local(inst(p)) of the
+// world ray and tri_ray of that local direction — values of the ray and the
+// placement alone, formed here once on entering p — and hit_triangle's
+// arithmetic on them; the winner is the smallest (t, first(p) + j) either
+// way, and a rigid transform leaves t what it is, so best_t clips both levels.
+// ---------------------------------------------------------------------------
+struct PoolView {
+  const DevObj *pool;
+  const int32_t *pool_j;
+  AttrView av;  // of_slot: top-level slot k, or sc.nobj + pool slot
+};
+__device__ __forceinline__ PoolView pool_view_of(const View &sc) {
+  const int32_t *hdr = sc.obj_id + sc.nobj;  // {pool slots, attribute records}
+  const DevObj *pool = sc.obj + sc.nobj;
+  const int32_t npool = hdr[0];
+  const AttrView av = hdr[1] > 0 ? AttrView{reinterpret_cast<const TriAttr *>(pool + npool), hdr + 2 + npool}
+                                 : AttrView{nullptr, nullptr};
+  return PoolView{pool, hdr + 2, av};
+}
+// the winner's insertion index: k a top-level slot, sub its pool slot when k is a placement (else -1)
+__device__ __forceinline__ int32_t inst_winner_id(const View &sc, int32_t k, int32_t sub) {
+  return sub >= 0 ? sc.obj_id[k] + sc.obj_id[sc.nobj + 2 + sub] : sc.obj_id[k];
+}
+// ... and its hit record: the pool triangle under the placement's Inst is the
+// record of the flattened copy (make_rec, attribute path included)
+__device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t sub, V ow, V dw, float time, float t,
+                                             int face) {
+  const PoolView pv = pool_view_of(sc);
+  const int32_t slot = sub >= 0 ? sc.nobj + sub : k;
+  DevObj ob = sc.obj[slot];
+  if (sub >= 0) ob.inst = sc.obj[k].inst;
+  return make_rec<false, 2>(sc, ob, ow, dw, time, t, face, pv.av, slot);
+}
+
+// hit_world_nw over a scene with placements.  One loop walks both levels: at
+// the top as hit_world_nw does; a leaf that holds a placement switches the
+// walk to that mesh's nodes with the ray taken to the placement's frame
+// (to_local, then the triangle constants and the slab inverses of the local
+// ray: once per entered placement), and the end of the mesh's nodes resumes
+// the top level behind the placement's leaf with the world ray's inverses.
+// Returns the winner's top-level slot (a placement's: best_sub is its pool
+// slot, else -1) or nobj + m for medium m; -1 none.
+template <bool LDS_NODES, bool LDS_OBJS>
+__device__ __forceinline__ int32_t hit_world_nw_inst(const View &sc, V o, V d, float time, uint64_t seg_key, float &best_t,
+                                                     int &best_face, int32_t &best_sub, NwCount *cnt) {
+  const float4 *nlo = LDS_NODES ? nw_nodes_lds : sc.nlo;
+  const float4 *nhi = LDS_NODES ? nw_nodes_lds + sc.nnodes : sc.nhi;
+  const DevObj *objs = LDS_OBJS ? reinterpret_cast<const DevObj *>(nw_nodes_lds + 2 * sc.nnodes) : sc.obj;
+  const int32_t *oids = LDS_OBJS ? reinterpret_cast<const int32_t *>(nw_nodes_lds + 2 * sc.nnodes + 3 * sc.nobj) : sc.obj_id;
+  const float4 *bn = sc.nhi + sc.nnodes;  // bottom-level nodes: {bmin, skip}, {bmax, leaf} pairs
+  const DevObj *pool = sc.obj + sc.nobj;
+  const int32_t *pool_j = sc.obj_id + sc.nobj + 2;
+  best_t = INFINITY;
+  int32_t best = -1, best_id = 0x7fffffff;
+  best_face = -1;
+  best_sub = -1;
+  uint32_t med_hit = 0;
+  const V invw = mk(drcp(d.x), drcp(d.y), drcp(d.z));  // hit_object's planes
+  const float2 trw = tri_world<1>(d);
+  for (int32_t m = 0; m < sc.nmed; ++m) {
+    const Obj ob = sc.med[m];
+    const int32_t id = sc.med_id[m];
+    V lo = o, ld = d;
+    if (ob.inst >= 0) to_local(sc.inst[ob.inst], lo, ld);
+    float t;
+    if constexpr (RTMI_STATS) cnt->flop += 2 * nw_test_flop(ob.aux & 255, false) + 4 + (ob.inst >= 0 ? 15 : 0);
+    if (hit_medium(ob, id, lo, ld, d, time, seg_key, t) && !(t < 0.001f)) {
+      med_hit |= 1u << m;
+      if (t < best_t || (t == best_t && id < best_id)) {
+        best_t = t;
+        best = sc.nobj + m;
+        best_id = id;
+      }
+    }
+  }
+  auto safe_inv = [](float v) { return drcp(__builtin_fabsf(v) < 1e-20f ? __builtin_copysignf(1e-20f, v) : v); };
+  float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
+  float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
+  // inside a placement (resume >= 0): its local ray, triangle constants, record slot and first(p)
+  V co = o, cd = d;
+  TriRay ts{0.f, 0.f, 0.f};
+  int axes = 0;
+  int32_t ptop = -1, pfirst = 0;
+  int32_t node = 0, end = sc.nnodes, resume = -1;
+  for (;;) {
+    if (node >= end) {
+      if (resume < 0) break;
+      node = resume;  // back to the top level, behind the placement's leaf
+      end = sc.nnodes;
+      resume = -1;
+      co = o;
+      cd = d;
+      ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
+      ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
+      continue;
+    }
+    const bool bottom = resume >= 0;
+    float4 lo, hi;
+    if (bottom) {
+      lo = bn[2 * node];
+      hi = bn[2 * node + 1];
+    } else {
+      lo = nlo[node];
+      hi = nhi[node];
+    }
+    const float tx0 = __builtin_fmaf(lo.x, ix, ox), tx1 = __builtin_fmaf(hi.x, ix, ox);
+    const float ty0 = __builtin_fmaf(lo.y, iy, oy), ty1 = __builtin_fmaf(hi.y, iy, oy);
+    const float tz0 = __builtin_fmaf(lo.z, iz, oz), tz1 = __builtin_fmaf(hi.z, iz, oz);
+    const float tnear = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(tx0, tx1), __builtin_fminf(ty0, ty1)),
+                                        __builtin_fmaxf(__builtin_fminf(tz0, tz1), 0.0f));
+    const float tfar = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(tx0, tx1), __builtin_fmaxf(ty0, ty1)),
+                                       __builtin_fminf(__builtin_fmaxf(tz0, tz1), best_t));
+    const bool enter = tnear <= tfar;
+    const int32_t leaf = __float_as_int(hi.w);
+    if constexpr (RTMI_STATS) {
+      cnt->flop += 25;
+      cnt->nodes += 1;
+    }
+    if (enter && leaf >= 0) {
+      const int32_t first = leaf >> 4, nleaf = leaf & 15;
+      if (bottom) {
+        for (int32_t k = first; k < first + nleaf; ++k) {
+          const DevObj ob = pool[k];
+          if constexpr (RTMI_STATS) {
+            cnt->flop += nw_test_flop(kTriangle, false);
+            cnt->objects += 1;
+          }
+          V v0, v1, v2;
+          tri_vertices(ob, v0, v1, v2);
+          float U, Vv, W, det, T;  // hit_triangle with the axes formed once
+          const bool in = tri_edges(co, axes, ts, v0, v1, v2, U, Vv, W, det, T);
+          const float t = T / det;
+          const int32_t id = pfirst + pool_j[k];
+          if (in & (t >= 0.001f) && (t < best_t || (t == best_t && id < best_id))) {
+            best_t = t;
+            best = ptop;
+            best_sub = k;
+            best_id = id;
+            best_face = -1;
+          }
+        }
+      } else if ((objs[first].ka & 255) == kInstance) {  // (alone in its leaf)
+        const DevObj ob = objs[first];
+        if constexpr (RTMI_STATS) cnt->flop += 18;  // the ray transform and the triangle constants
+        resume = node + 1;
+        ptop = first;
+        node = __float_as_int(ob.g0[0]);
+        end = __float_as_int(ob.g0[1]);
+        pfirst = __float_as_int(ob.g0[3]);
+        if (ob.inst >= 0) to_local(sc.inst[ob.inst], co, cd);
+        // tri_ray of the local direction; without an Inst (or a rotation) it is
+        // the world ray's trw / invw selection of hit_object, value for value
+        axes = tri_axes(cd);
+        ts = tri_ray(cd);
+        ix = safe_inv(cd.x), iy = safe_inv(cd.y), iz = safe_inv(cd.z);
+        ox = -co.x * ix, oy = -co.y * iy, oz = -co.z * iz;
+        continue;
+      } else {
+        for (int32_t k = first; k < first + nleaf; ++k) {
+          const DevObj ob = objs[k];
+          const int twin = ob.ka >> 8;
+          if (twin > 0 && ((med_hit >> (twin - 1)) & 1u)) continue;  // hidden by its medium
+          if constexpr (RTMI_STATS) {
+            cnt->flop += nw_test_flop(ob.ka & 255, ob.inst >= 0);
+            cnt->objects += 1;
+          }
+          const int32_t id = oids[k];
+          float t;
+          int face = -1;
+          if (hit_object<false, 1>(sc, ob, o, d, invw, trw, time, t, face) && (t < best_t || (t == best_t && id < best_id))) {
+            best_t = t;
+            best = k;
+            best_sub = -1;
+            best_id = id;
+            best_face = face;
+          }
+        }
+      }
+    }
+    node = enter ? node + 1 : __float_as_int(lo.w);
+  }
+  return best;
 }
 
 // ---------------------------------------------------------------------------

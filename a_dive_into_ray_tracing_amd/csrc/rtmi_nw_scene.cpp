@@ -23,7 +23,7 @@ using namespace rtmi::nw;
 
 namespace {
 
-enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4 };
+enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4, kShared = 5 };
 
 struct SNode {
   int type = kPrim;
@@ -31,7 +31,7 @@ struct SNode {
   int32_t attr = -1;           // kPrim, a triangle: its attribute record (rt_nw_scene::attr) or -1
   double g[12] = {0};          // kPrim geometry, double (layout of Obj g0..g2)
   std::vector<int32_t> kids;   // kGroup
-  int32_t child = -1;          // kTranslate / kRotate / kMediumNode
+  int32_t child = -1;          // kTranslate / kRotate / kMediumNode / kShared
   double off[3] = {0, 0, 0};   // kTranslate
   double angle = 0;            // kRotate (degrees)
   double density = 0;          // kMediumNode
@@ -113,6 +113,14 @@ struct rt_nw_scene {
   std::vector<int32_t> flat_attr; // its attribute record or -1 (rt_nw_scene_flat_attr)
   std::vector<Bounds> flat_bounds;
   std::vector<Inst> flat_inst;
+  // every occurrence of a shared handle (rt_nw_shared) reached from the world:
+  // its kShared node, composed transform, and the flattened objects it
+  // expanded to, [first, first + count)
+  struct Place {
+    int32_t node, first, count;
+    Xf x;
+  };
+  std::vector<Place> flat_place;
 };
 
 namespace {
@@ -299,6 +307,12 @@ struct Flattener {
         return;
       case kTranslate: emit(n.child, compose_translate(x, n.off), depth + 1); return;
       case kRotate: emit(n.child, compose_rotate(x, n.angle), depth + 1); return;
+      case kShared: {  // the flat view is the expansion; the placement is remembered for the device scene
+        const int32_t first = int32_t(s->flat_obj.size());
+        emit(n.child, x, depth + 1);
+        if (!err) s->flat_place.push_back(rt_nw_scene::Place{id, first, int32_t(s->flat_obj.size()) - first, x});
+        return;
+      }
       case kMediumNode: {
         int32_t prim = -1;
         Xf xb;
@@ -335,6 +349,7 @@ int flatten(rt_nw_scene *s) {
   s->flat_attr.clear();
   s->flat_bounds.clear();
   s->flat_inst.clear();
+  s->flat_place.clear();
   Flattener f{s, {}, RT_OK};
   for (int32_t id : s->world) f.emit(id, Xf{}, 0);
   if (f.err) return f.err;
@@ -370,6 +385,7 @@ struct ObjBvh {
   const std::vector<double> &m;  // per-object box margin
   std::vector<Node> nodes;
   std::vector<int32_t> order;
+  const std::vector<char> *solo = nullptr;  // objects that get a leaf of their own (placements); null: none
 
   static double area(const double lo[3], const double hi[3]) {
     const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
@@ -433,7 +449,10 @@ struct ObjBvh {
 #define RTMI_NW_KTRAV 2.0
 #endif
     const double kTrav = RTMI_NW_KTRAV;  // a node visit against one sphere test
-    const bool leaf = cnt == 1 || (cnt <= kNodeLeafMax && pa * wsum <= kTrav * pa + best);
+    bool may_share = true;
+    if (solo)
+      for (int i = 0; i < cnt; ++i) may_share = may_share && !(*solo)[ids[i]];
+    const bool leaf = cnt == 1 || (may_share && cnt <= kNodeLeafMax && pa * wsum <= kTrav * pa + best);
     if (leaf) {
       nd.leaf = (int32_t(order.size()) << 4) | cnt;
       for (int i = 0; i < cnt; ++i) order.push_back(ids[i]);
@@ -561,6 +580,66 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   if (int rc = flatten(s)) return rc;
   const int n_all = int(s->flat_obj.size());
   if (n_all == 0) return set_error(RT_EINVAL, "rt_nw: empty world (rt_nw_world_add)");
+  out.mesh.clear();
+  out.place_mesh.clear();
+  out.place_slot.clear();
+  out.pool.clear();
+  out.pool_j.clear();
+  out.pool_attr.clear();
+  out.bnodes.clear();
+  // Shared meshes (DESIGN.md §9 "Shared meshes"): the flattened objects of a
+  // placement stay out of the top level; the placement itself joins it as
+  // object n_all + p, bounded by its mesh's local box under its transform.
+  // A mesh's triangles are those of its first placement's expansion (the
+  // geometry of every expansion is the same; only `inst` differs).
+  const std::vector<rt_nw_scene::Place> &places = s->flat_place;
+  const int n_place = int(places.size());
+  struct MeshBuild {
+    int32_t first;                // its first placement's first flattened object
+    std::vector<Bounds> lb;       // per triangle j, local space
+    std::vector<int32_t> tris;    // the j that are not collinear
+    Bounds box;                   // their union
+  };
+  std::vector<MeshBuild> mb;
+  std::vector<char> placed;
+  std::vector<Bounds> with_places;  // flat_bounds, then one box per placement
+  if (n_place > 0) {
+    placed.assign(size_t(n_all), 0);
+    std::map<int32_t, int32_t> mesh_of_node;
+    for (const rt_nw_scene::Place &p : places) {
+      for (int32_t k = p.first; k < p.first + p.count; ++k) placed[size_t(k)] = 1;
+      auto it = mesh_of_node.find(p.node);
+      if (it == mesh_of_node.end()) {
+        it = mesh_of_node.emplace(p.node, int32_t(mb.size())).first;
+        MeshBuild m;
+        m.first = p.first;
+        for (int a = 0; a < 3; ++a) {
+          m.box.lo[a] = INFINITY;
+          m.box.hi[a] = -INFINITY;
+        }
+        m.lb.resize(size_t(p.count));
+        for (int32_t j = 0; j < p.count; ++j) {
+          const Obj &o = s->flat_obj[size_t(p.first + j)];
+          if (o.kind != kTriangle) return set_error(RT_EINVAL, "rt_nw: shared geometry holds a non-triangle");
+          m.lb[size_t(j)] = local_bounds(s->nodes[size_t(s->flat_src[size_t(p.first + j)])], kTriangle);
+          if (collinear_triangle(o)) continue;  // never hit: keeps its index j, joins no BVH
+          m.tris.push_back(j);
+          for (int a = 0; a < 3; ++a) {
+            m.box.lo[a] = std::min(m.box.lo[a], m.lb[size_t(j)].lo[a]);
+            m.box.hi[a] = std::max(m.box.hi[a], m.lb[size_t(j)].hi[a]);
+          }
+        }
+        mb.push_back(std::move(m));
+        out.mesh.push_back(DeviceScene::SharedMesh{0, 0, 0, 0, p.count});
+      }
+      out.place_mesh.push_back(it->second);
+      if (out.mesh[size_t(it->second)].n_tris != p.count) return set_error(RT_EINVAL, "rt_nw: placements of one mesh differ");
+    }
+    with_places = s->flat_bounds;
+    for (int pi = 0; pi < n_place; ++pi) with_places.push_back(world_bounds(mb[size_t(out.place_mesh[size_t(pi)])].box, places[size_t(pi)].x));
+  }
+  const std::vector<Bounds> &bounds = n_place > 0 ? with_places : s->flat_bounds;
+  const int n_ext = n_all + n_place;
   // media are evaluated per segment before the BVH walk;
   // the BVH holds the other objects
   std::vector<int32_t> med_index(n_all, -1), ids;
@@ -571,6 +650,8 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       med_index[k] = int32_t(out.med.size());
       out.med.push_back(s->flat_obj[k]);
       out.med_id.push_back(k);
+    } else if (n_place > 0 && placed[size_t(k)]) {
+      // reached through its placement's record
     } else if (collinear_triangle(s->flat_obj[k])) {
       // never hit (rt_nw_triangle): it keeps its insertion index and joins
       // neither the BVH nor the grid
@@ -578,9 +659,11 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       ids.push_back(k);
     }
   }
+  for (int pi = 0; pi < n_place; ++pi)  // (a mesh of collinear triangles only is never hit: no record)
+    if (!mb[size_t(out.place_mesh[size_t(pi)])].tris.empty()) ids.push_back(n_all + pi);
   double scale = 0;
   for (int32_t k : ids) {
-    const Bounds &b = s->flat_bounds[k];
+    const Bounds &b = bounds[k];
     for (int a = 0; a < 3; ++a) {
       if (!std::isfinite(b.lo[a]) || !std::isfinite(b.hi[a]))
         return set_error(RT_EINVAL, "rt_nw: object with non-finite bounds");
@@ -589,45 +672,124 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   }
   // relative test costs: a box is six rectangle tests, a triangle ~47 flop
   // against a sphere's ~30 with its square root, an instance adds a ray
-  // transform
-  std::vector<double> cost(n_all, 1.0);
+  // transform; a placement is a walk of its own (a guess: a few node visits
+  // and triangle tests)
+  std::vector<double> cost(n_ext, 1.0);
   for (int k = 0; k < n_all; ++k) {
     const Obj &o = s->flat_obj[k];
     cost[k] = (o.kind == kBox ? 3.0 : o.kind == kMovingSphere ? 1.2 : o.kind == kTriangle ? 1.5 : 1.0) + (o.inst >= 0 ? 0.3 : 0.0);
   }
+  for (int k = n_all; k < n_ext; ++k) cost[k] = 8.0;
   // box margins (the RTIOW BVH's argument): 1e-3 of the
   // object's own coordinate scale — ~100x the float error of its hit test —
   // plus 1e-6 of the scene's, for rays from far away.  One scene-wide margin
   // of 1e-3 of the scene scale grew every small box by ~2 units next to the
   // R = 1000 ground (137 node visits per camera ray instead of ~20).
-  std::vector<double> margin(n_all, 0.0);
+  std::vector<double> margin(n_ext, 0.0);
   for (int32_t k : ids) {
     double own = 0;
     for (int a = 0; a < 3; ++a)
-      own = std::max(own, std::max(std::fabs(s->flat_bounds[k].lo[a]), std::fabs(s->flat_bounds[k].hi[a])));
+      own = std::max(own, std::max(std::fabs(bounds[k].lo[a]), std::fabs(bounds[k].hi[a])));
     margin[k] = 1e-3 * (1.0 + own) + 1e-6 * scale;
   }
-  ObjBvh bvh{s->flat_bounds, cost, margin, {}, {}};
+  std::vector<char> solo;
+  if (n_place > 0) {
+    solo.assign(size_t(n_ext), 0);
+    for (int k = n_all; k < n_ext; ++k) solo[size_t(k)] = 1;
+  }
+  ObjBvh bvh{bounds, cost, margin, {}, {}};
+  if (n_place > 0) bvh.solo = &solo;  // the walk enters a placement from a leaf of its own
   const int n = int(ids.size());
   if (n > 0) bvh.build(ids.data(), n);
   out.nodes = std::move(bvh.nodes);
+  // bottom level: one BVH per placed mesh over its triangles in local space,
+  // margins as above with the mesh's own scale beside the scene's (a local ray
+  // starts as far away as the world ray does)
+  for (size_t mi = 0; mi < mb.size(); ++mi) {
+    const MeshBuild &m = mb[mi];
+    DeviceScene::SharedMesh &M = out.mesh[mi];
+    M.node0 = int32_t(out.bnodes.size());
+    M.pool0 = int32_t(out.pool.size());
+    if (m.tris.empty()) continue;
+    double lscale = scale;
+    for (int a = 0; a < 3; ++a) lscale = std::max(lscale, std::max(std::fabs(m.box.lo[a]), std::fabs(m.box.hi[a])));
+    std::vector<double> lcost(m.lb.size(), 1.5), lmargin(m.lb.size(), 0.0);
+    for (int32_t j : m.tris) {
+      double own = 0;
+      for (int a = 0; a < 3; ++a)
+        own = std::max(own, std::max(std::fabs(m.lb[size_t(j)].lo[a]), std::fabs(m.lb[size_t(j)].hi[a])));
+      lmargin[size_t(j)] = 1e-3 * (1.0 + own) + 1e-6 * lscale;
+    }
+    ObjBvh lb{m.lb, lcost, lmargin, {}, {}};
+    std::vector<int32_t> lids = m.tris;
+    lb.build(lids.data(), int(lids.size()));
+    if (out.pool.size() + lb.order.size() >= (size_t(1) << 27) || out.bnodes.size() + lb.nodes.size() >= (size_t(1) << 30))
+      return set_error(RT_EINVAL, "rt_nw: shared meshes too large");
+    M.n_nodes = int32_t(lb.nodes.size());
+    M.n_pool = int32_t(lb.order.size());
+    for (Node nd : lb.nodes) {  // absolute links: into bnodes and into the pool
+      nd.skip += M.node0;
+      if (nd.leaf >= 0) nd.leaf = ((M.pool0 + (nd.leaf >> 4)) << 4) | (nd.leaf & 15);
+      out.bnodes.push_back(nd);
+    }
+    for (int32_t j : lb.order) {
+      Obj o = s->flat_obj[size_t(m.first + j)];
+      o.inst = -1;
+      o.aux = 0;
+      out.pool.push_back(o);
+      out.pool_j.push_back(j);
+    }
+  }
   out.obj.resize(n);
   out.obj_id.resize(n);
   out.attr.clear();
   out.obj_attr.clear();
-  for (int k = 0; k < n; ++k)
-    if (s->flat_attr[bvh.order[k]] >= 0) {  // some object carries an attribute record: the locator exists
-      out.attr = s->attr;
-      out.obj_attr.resize(n);
-      break;
-    }
+  bool any_attr = false;
+  for (int k = 0; k < n && !any_attr; ++k) any_attr = bvh.order[k] < n_all && s->flat_attr[bvh.order[k]] >= 0;
+  for (size_t mi = 0; mi < mb.size() && !any_attr; ++mi)
+    for (size_t q = 0; q < size_t(out.mesh[mi].n_pool) && !any_attr; ++q)
+      any_attr = s->flat_attr[size_t(mb[mi].first + out.pool_j[size_t(out.mesh[mi].pool0) + q])] >= 0;
+  if (any_attr) {  // some object carries an attribute record: the locators exist
+    out.attr = s->attr;
+    out.obj_attr.resize(n);
+    for (size_t mi = 0; mi < mb.size(); ++mi)
+      for (size_t q = 0; q < size_t(out.mesh[mi].n_pool); ++q)
+        out.pool_attr.push_back(s->flat_attr[size_t(mb[mi].first + out.pool_j[size_t(out.mesh[mi].pool0) + q])]);
+  }
+  out.place_slot.assign(size_t(n_place), -1);
   for (int k = 0; k < n; ++k) {
+    if (bvh.order[k] >= n_all) {  // a placement's record (rtmi_nw_types.h kInstance)
+      const int pi = bvh.order[k] - n_all;
+      const rt_nw_scene::Place &p = places[size_t(pi)];
+      const DeviceScene::SharedMesh &M = out.mesh[size_t(out.place_mesh[size_t(pi)])];
+      Obj o{};
+      const int32_t w[4] = {M.node0, M.node0 + M.n_nodes, M.pool0, p.first};
+      std::memcpy(o.g0, w, sizeof w);
+      std::memcpy(&o.g1[0], &M.n_pool, 4);
+      o.kind = kInstance;
+      o.mat = 0;
+      o.inst = s->flat_obj[size_t(p.first)].inst;  // every object of the expansion carries the same one
+      o.aux = 0;
+      out.obj[k] = o;
+      out.obj_id[k] = p.first;
+      if (any_attr) out.obj_attr[k] = -1;
+      out.place_slot[size_t(pi)] = k;
+      continue;
+    }
     out.obj[k] = s->flat_obj[bvh.order[k]];
     out.obj_id[k] = bvh.order[k];
-    if (!out.obj_attr.empty()) out.obj_attr[k] = s->flat_attr[bvh.order[k]];
+    if (any_attr) out.obj_attr[k] = s->flat_attr[bvh.order[k]];
     if (out.obj[k].aux > 0) out.obj[k].aux = med_index[out.obj[k].aux - 1] + 1;  // twin -> media-list index + 1
   }
-  build_obj_grid(s->flat_bounds, margin, bvh.order, out);
+  if (n_place > 0) {  // no uniform grid over placements (out of scope): such a scene renders with the BVH
+    out.grid_ok = false;
+    out.grid_max_cell = 0;
+    out.grid_cell_start.clear();
+    out.grid_refs.clear();
+    out.grid_big.clear();
+  } else {
+    build_obj_grid(s->flat_bounds, margin, bvh.order, out);
+  }
   out.inst = s->flat_inst;
   out.mat = s->mat;
   out.tex = s->tex;
@@ -637,6 +799,19 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   out.image = s->image;
   for (int c = 0; c < 3; ++c) out.background[c] = s->background[c];
   out.has_media = !out.med.empty();
+  return RT_OK;
+}
+
+int scene_instancing_stats(rt_nw_scene *s, int32_t out6[6]) {
+  if (!out6) return set_error(RT_EINVAL, "rt_nw_scene_instancing_stats: null");
+  DeviceScene ds;
+  if (int rc = build_device_scene(s, ds)) return rc;
+  out6[0] = int32_t(ds.mesh.size());
+  out6[1] = int32_t(ds.place_mesh.size());
+  out6[2] = int32_t(ds.pool.size());
+  out6[3] = int32_t(ds.bnodes.size());
+  out6[4] = int32_t(ds.obj.size());
+  out6[5] = int32_t(ds.nodes.size());
   return RT_OK;
 }
 
@@ -1171,8 +1346,9 @@ RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, in
 // the mesh's lambertian or metal material.
 namespace {
 int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb, int32_t w, int32_t h,
-              double aspect, rt_nw_camera *cam, int32_t *n_tris) {
+              double aspect, rt_nw_camera *cam, int32_t *n_tris, int32_t copies = 1) {
   if (!s || !path || !cam || !(aspect > 0) || !mesh_flags_ok(flags)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
+  if (copies < 1 || copies > 256) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: copies must be in 1..256");
   if (mat_kind != RT_NW_LAMBERTIAN && mat_kind != RT_NW_METAL && mat_kind != RT_NW_DIELECTRIC)
     return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: material must be lambertian, metal or dielectric");
   if (rgb && mat_kind == RT_NW_DIELECTRIC) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: a dielectric takes no texture image");
@@ -1207,12 +1383,30 @@ int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags
   const int light = chk(rt_nw_rect(s, RT_NW_XZ, -1.5, 1.5, -1.5, 1.5, 5.0, chk(rt_nw_mat_diffuse_light(s, chk(rt_nw_tex_solid(s, 6, 6, 6))))));
   if (rc) return rc;
   chk(rt_nw_world_add(s, ground));
-  chk(rt_nw_world_add(s, mesh));
+  if (copies == 1) {
+    chk(rt_nw_world_add(s, mesh));
+  } else {
+    // copies x copies placements of the one shared mesh, 3 units apart and
+    // centred on the origin; copy (i, k) is turned by 37 (i * copies + k)
+    // degrees, and nudged by up to 0.4 units along x and z (a fixed formula)
+    const int shared = chk(rt_nw_shared(s, mesh));
+    if (rc) return rc;
+    for (int i = 0; i < copies; ++i)
+      for (int k = 0; k < copies; ++k) {
+        const int q = i * copies + k;
+        const double off[3] = {3.0 * (i - 0.5 * (copies - 1)) + 0.4 * std::sin(1.7 * q), 0.0,
+                               3.0 * (k - 0.5 * (copies - 1)) + 0.4 * std::cos(2.3 * q)};
+        chk(rt_nw_world_add(s, chk(rt_nw_translate(s, chk(rt_nw_rotate_y(s, shared, 37.0 * q)), off))));
+        if (rc) return rc;
+      }
+  }
   chk(rt_nw_world_add(s, light));
   chk(rt_nw_set_background(s, 0.05, 0.07, 0.12));
   if (rc) return rc;
-  const double from[3] = {3.2, 2.4, 4.8}, at[3] = {0, 1, 0}, vup[3] = {0, 1, 0};
-  const double dist = std::sqrt(3.2 * 3.2 + 1.4 * 1.4 + 4.8 * 4.8);
+  // the camera backs away along its line of sight with the field's extent
+  const double back = copies == 1 ? 1.0 : 0.5 + 0.75 * copies;
+  const double from[3] = {3.2 * back, copies == 1 ? 2.4 : 1.0 + 1.4 * back, 4.8 * back}, at[3] = {0, 1, 0}, vup[3] = {0, 1, 0};
+  const double dist = std::sqrt(3.2 * 3.2 + 1.4 * 1.4 + 4.8 * 4.8) * back;
   return rt_nw_camera_init(cam, from, at, vup, 30.0, aspect, 0.0, dist, 0.0, 1.0);
 }
 }  // namespace
@@ -1228,13 +1422,19 @@ RTMI_EXPORT int rt_nw_scene_obj_stage_attr(rt_nw_scene *s, const char *path, int
   return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris);
 }
 
+RTMI_EXPORT int rt_nw_scene_obj_stage_copies(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags,
+                                             const uint8_t *rgb, int32_t w, int32_t h, int32_t copies, double aspect,
+                                             rt_nw_camera *cam, int32_t *n_tris) {
+  return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris, copies);
+}
+
 RTMI_EXPORT int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex) {
   if (!s || !valid_node(s, boundary) || !valid_tex(s, tex) || !(density > 0))
     return set_error(RT_EINVAL, "rt_nw_constant_medium: bad argument");
   {  // a triangle (under any translate / rotate_y chain) bounds no volume
     int32_t b = boundary;
     while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate)) b = s->nodes[b].child;
-    if (valid_node(s, b) && s->nodes[b].type == kPrim && s->nodes[b].kind == kTriangle)
+    if (valid_node(s, b) && ((s->nodes[b].type == kPrim && s->nodes[b].kind == kTriangle) || s->nodes[b].type == kShared))
       return set_error(RT_EUNSUPPORTED, "rt_nw_constant_medium: a triangle cannot be a medium's boundary");
   }
   const int m = rt_nw_mat_isotropic(s, tex);  // phase_function = new isotropic(a) constant_medium.h:12-17
@@ -1282,6 +1482,39 @@ RTMI_EXPORT int rt_nw_rotate_y(rt_nw_scene *s, int32_t object, double angle_deg)
   n.child = object;
   n.angle = angle_deg;
   return add_node(s, n);
+}
+
+namespace {
+// the subtree of a shared handle: triangles and groups of them; counts the triangles
+int shared_subtree(const rt_nw_scene *s, int32_t id, int depth, int64_t &n_tris) {
+  if (depth > 64) return set_error(RT_EINVAL, "rt_nw_shared: object nesting deeper than 64 (a cycle?)");
+  const SNode &n = s->nodes[size_t(id)];
+  if (n.type == kPrim && n.kind == kTriangle) {
+    ++n_tris;
+    return RT_OK;
+  }
+  if (n.type == kGroup) {
+    for (int32_t k : n.kids)
+      if (int rc = shared_subtree(s, k, depth + 1, n_tris)) return rc;
+    return RT_OK;
+  }
+  return set_error(RT_EUNSUPPORTED, "rt_nw_shared: only triangles and groups of them can be shared geometry");
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_shared(rt_nw_scene *s, int32_t object) {
+  if (!s || !valid_node(s, object)) return set_error(RT_EINVAL, "rt_nw_shared: bad argument");
+  int64_t n_tris = 0;
+  if (int rc = shared_subtree(s, object, 0, n_tris)) return rc;
+  if (n_tris == 0) return set_error(RT_EINVAL, "rt_nw_shared: no triangle under object %d", object);
+  SNode n;
+  n.type = kShared;
+  n.child = object;
+  return add_node(s, n);
+}
+
+RTMI_EXPORT int rt_nw_scene_instancing_stats(rt_nw_scene *s, int32_t out[6]) {
+  return rtmi::nw::scene_instancing_stats(s, out);
 }
 
 RTMI_EXPORT int rt_nw_world_add(rt_nw_scene *s, int32_t object) {

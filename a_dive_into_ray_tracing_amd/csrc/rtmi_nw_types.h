@@ -20,6 +20,11 @@ enum ObjKind : int32_t {
                       //                     aux >> 8 = scattering-distance samples
   kTriangle = 7,      // triangle (two-sided, watertight): the vertices as nine floats,
                       //                     g0 = {v0, v1.x}, g1 = {v1.y, v1.z, v2.x, v2.y}, g2.x = v2.z
+  kInstance = 8,      // one placement of a shared mesh (rt_nw_shared; device scene only, never in the flat
+                      //                     view): g0 as int32 bits = {first bottom-level node, one past its
+                      //                     last, first pool slot, first(p): the insertion index of the
+                      //                     placement's triangle 0}, g1.x as int32 bits = pool slots of the mesh;
+                      //                     inst = the placement's Inst or -1 (DESIGN.md §9 "Shared meshes")
 };
 
 // material kinds = RT_NW_* (rtmi_nw.h)

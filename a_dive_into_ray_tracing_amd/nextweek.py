@@ -185,6 +185,13 @@ class Scene:
     def rotate_y(self, obj, angle):
         return _id(load().rt_nw_rotate_y(self._h, obj, float(angle)), "rt_nw_rotate_y")
 
+    def shared(self, obj):
+        """`obj` (triangles, meshes and groups of them) as shared geometry: a
+        handle to translate, rotate_y, group and add any number of times; the
+        device holds the triangles once and one small record per placement, and
+        the image is that of the copies, bit for bit (rt_nw_shared)."""
+        return _id(load().rt_nw_shared(self._h, obj), "rt_nw_shared")
+
     def add(self, obj):
         check(load().rt_nw_world_add(self._h, obj), "rt_nw_world_add")
         return self
@@ -219,6 +226,15 @@ class Scene:
               "rt_nw_scene_grid_stats")
         return {"dims": tuple(dims), "max_cell": mc.value, "n_big": nb.value, "n_refs": nr.value}
 
+    def instancing_stats(self):
+        """What a device context would build of the shared meshes (host only,
+        rt_nw_scene_instancing_stats): {"meshes", "placements", "pool_triangles",
+        "bottom_nodes", "top_leaves", "top_nodes"}; the first four are 0 in a
+        scene without a placement."""
+        v = (C.c_int32 * 6)()
+        check(load().rt_nw_scene_instancing_stats(self._h, v), "rt_nw_scene_instancing_stats")
+        return dict(zip(("meshes", "placements", "pool_triangles", "bottom_nodes", "top_leaves", "top_nodes"), list(v)))
+
     def close(self):
         if self._h:
             load().rt_nw_scene_destroy(self._h)
@@ -252,15 +268,28 @@ def _mesh_flags(smooth, uv, gen_normals):
     return (1 if smooth else 0) | (2 if uv else 0) | (4 if gen_normals else 0)
 
 
-def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None):
+def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None, copies=1):
     """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera:
     (scene, camera, triangle count).  smooth / gen_normals as Scene.load_obj;
     texture (h x w x 3 uint8): the mesh's texture, mapped by the file's vt
-    (rt_nw_scene_obj_stage_attr; none of them: rt_nw_scene_obj_stage)."""
+    (rt_nw_scene_obj_stage_attr; none of them: rt_nw_scene_obj_stage).
+    copies = N > 1 (`--obj-copies N`): the model as one shared mesh placed in an
+    N x N field (rt_nw_scene_obj_stage_copies)."""
     kind = {"lambertian": 0, "metal": 1, "glass": 2, "dielectric": 2}[mat]
     s = Scene()
     cam = RtNwCamera()
     n = C.c_int32()
+    if copies != 1:
+        if texture is not None:
+            a = np.ascontiguousarray(texture, np.uint8)
+            ptr, ih, iw = a.ctypes.data_as(_u8), a.shape[0], a.shape[1]
+        else:
+            ptr, ih, iw = None, 0, 0
+        check(load().rt_nw_scene_obj_stage_copies(s._h, str(path).encode(), kind,
+                                                  _mesh_flags(smooth, texture is not None, gen_normals), ptr, iw, ih,
+                                                  int(copies), float(aspect), C.byref(cam), C.byref(n)),
+              "rt_nw_scene_obj_stage_copies")
+        return s, cam, n.value
     if not (smooth or gen_normals) and texture is None:
         check(load().rt_nw_scene_obj_stage(s._h, str(path).encode(), kind, float(aspect), C.byref(cam), C.byref(n)),
               "rt_nw_scene_obj_stage")

@@ -145,9 +145,20 @@ int rt_nw_load_obj_attr(rt_nw_scene *s, const char *path, int32_t mat, uint32_t 
  * lambertian or metal material (with RT_NW_DIELECTRIC: RT_EINVAL). */
 int rt_nw_scene_obj_stage_attr(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
                                int32_t w, int32_t h, double aspect, rt_nw_camera *cam, int32_t *n_tris);
+/* rt_nw_scene_obj_stage_attr with the mesh staged copies x copies times as one
+ * shared mesh (rt_nw_shared): a field on the checker ground, 3 units between
+ * neighbours, centred on the origin; copy q = i * copies + k (i along x, k
+ * along z) is rotate_y(37 q degrees), then translated to
+ * (3 (i - (copies - 1) / 2) + 0.4 sin(1.7 q), 0, 3 (k - (copies - 1) / 2) +
+ * 0.4 cos(2.3 q)); the camera keeps its line of sight and stands 0.5 + 0.75
+ * copies times as far away.  copies == 1: rt_nw_scene_obj_stage_attr exactly
+ * (no shared handle).  copies outside 1..256: RT_EINVAL. */
+int rt_nw_scene_obj_stage_copies(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
+                                 int32_t w, int32_t h, int32_t copies, double aspect, rt_nw_camera *cam, int32_t *n_tris);
 /* constant_medium(boundary, density, tex) constant_medium.h: boundary is a
  * sphere, moving sphere or box object, optionally under translate/rotate_y
- * (a rectangle, a triangle or a set of objects: RT_EUNSUPPORTED). */
+ * (a rectangle, a triangle, a shared handle or a set of objects:
+ * RT_EUNSUPPORTED). */
 int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex);
 /* Scattering-distance samples of a medium per ray segment (1..8, default 1):
  * each draws -log(u)/density anew and the last one that lands inside the
@@ -162,6 +173,22 @@ int rt_nw_medium_samples(rt_nw_scene *s, int32_t medium, int32_t samples);
 int rt_nw_group(rt_nw_scene *s, const int32_t *objects, int32_t n);
 int rt_nw_translate(rt_nw_scene *s, int32_t object, const double offset[3]); /* hittable.h:49-88  */
 int rt_nw_rotate_y(rt_nw_scene *s, int32_t object, double angle_deg);       /* hittable.h:90-189 */
+/* `object` as shared geometry: a new handle, used like any object handle (in
+ * rt_nw_group, rt_nw_translate, rt_nw_rotate_y, rt_nw_world_add) any number of
+ * times; every occurrence reached from the world is one placement.  The scene
+ * renders exactly — bit for bit — as if `object` itself stood at every
+ * occurrence, and rt_nw_scene_flat / _flat_attr return that expansion
+ * (insertion order and `inst` table included: placement p's triangle j, in the
+ * subtree's flatten order, has insertion index first(p) + j).  The device
+ * holds the triangles once, under a bottom-level BVH of their own, and one
+ * small record per placement (DESIGN.md §9 "Shared meshes"); a scene with a
+ * placement has no uniform grid and renders with the BVH.
+ * The subtree of `object` may hold only triangles and groups of them (the
+ * handles of rt_nw_triangle, rt_nw_mesh, rt_nw_mesh_attr, rt_nw_load_obj* and
+ * rt_nw_group over those): anything else under it — another primitive kind,
+ * a translate or rotate node, a medium, another shared handle — is
+ * RT_EUNSUPPORTED; no triangle under it: RT_EINVAL. */
+int rt_nw_shared(rt_nw_scene *s, int32_t object);
 int rt_nw_world_add(rt_nw_scene *s, int32_t object);
 int rt_nw_set_background(rt_nw_scene *s, double r, double g, double b);
 
@@ -215,13 +242,23 @@ int rt_nw_scene_flat_attr(rt_nw_scene *s, int32_t *n_attr, const float **attr, c
  * the fullest cell's object count, the brute-force list's length and the
  * total cell references.  Any output may be null. */
 int rt_nw_scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *max_cell, int32_t *n_big, int32_t *n_refs);
+/* Host only: what rt_nw_ctx_set_scene would build of the scene's shared meshes
+ * (rt_nw_shared) — {shared meshes that are placed, placements, triangles in
+ * the shared pools (each mesh once, collinear triangles left out), bottom-level
+ * BVH nodes in total, top-level leaf records (objects outside placements + one
+ * per placement), top-level BVH nodes}.  Without a placement the first four
+ * are zero. */
+int rt_nw_scene_instancing_stats(rt_nw_scene *s, int32_t out[6]);
 
 /* ---- device ------------------------------------------------------------ */
 int rt_nw_ctx_create(int32_t device, rt_nw_ctx **out);
 int rt_nw_ctx_destroy(rt_nw_ctx *ctx);
 /* Flatten, build the BVH, upload.  Synchronous. */
 int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s);
-/* n_prims, n_nodes of the resident BVH */
+/* n_prims, n_nodes of the resident BVH.  In a scene with placements of shared
+ * meshes these are the top level's: its leaf records (one per placement and
+ * per object outside placements, plus the media) and its nodes; the pools and
+ * bottom-level nodes are counted by rt_nw_scene_instancing_stats. */
 int rt_nw_ctx_info(rt_nw_ctx *ctx, int32_t *n_prims, int32_t *n_nodes);
 /* Closest-hit structure over the non-media objects (media are always tested
  * first).  RT_NW_ACCEL_BVH: the SAH BVH (skip-link walk).
