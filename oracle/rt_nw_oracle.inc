@@ -9,24 +9,18 @@
  * policy of DESIGN.md §9.  It reads the FLATTENED scene (rt_nw_scene_flat,
  * insertion order) and finds closest hits by brute force over every object —
  * no BVH — so the GPU's BVH, leaf order and traversal are checked against
- * the plain list.  Parity with the CUDA reference itself is statistical only
- * (tests/test_nw_gpu.py): the reference cannot run here.
+ * the plain list.  Triangles (kind 7) and their attribute records are written
+ * from the two specification comments of csrc/rtmi_nw_path.h alone: a third
+ * restatement beside the kernels and tests/native/nw_*_ref.cpp.  An object
+ * kind this file does not know is refused by every entry point.  Parity
+ * with the CUDA reference itself is statistical only (tests/test_nw_gpu.py):
+ * the reference cannot run here.
  */
 
-typedef struct or_nw_scene {
-  int32_t n_obj, n_inst;
-  const float *obj;       /* 16 per object: g0[4] g1[4] g2[4] kind mat inst aux (int bits) */
-  const float *inst;      /* 8 per instance: c s ox oy oz flags(int bits) 0 0 */
-  const float *mat;       /* 4 per material: kind tex (int bits) fuzz ir */
-  const float *tex;       /* 8 per texture: kind a b 0 (int bits) r g b scale */
-  const float *perlin_vec;    /* 256 * 4 per perlin */
-  const int32_t *perlin_perm; /* 768 per perlin */
-  const int32_t *image_desc;  /* 4 per image: offset w h 0 */
-  const uint8_t *image_px;
-  float bg[3];
-} or_nw_scene;
+/* or_nw_scene and the entry points' prototypes: rt_oracle.h */
 
-enum { NW_SPHERE = 0, NW_MOVING = 1, NW_XY = 2, NW_XZ = 3, NW_YZ = 4, NW_BOX = 5, NW_MEDIUM = 6 };
+enum { NW_SPHERE = 0, NW_MOVING = 1, NW_XY = 2, NW_XZ = 3, NW_YZ = 4, NW_BOX = 5, NW_MEDIUM = 6, NW_TRIANGLE = 7,
+       NW_KINDS = 8 };
 enum { NWM_LAMB = 0, NWM_METAL = 1, NWM_DIEL = 2, NWM_LIGHT = 3, NWM_ISO = 4 };
 enum { NWT_SOLID = 0, NWT_CHECKER = 1, NWT_NOISE = 2, NWT_IMAGE = 3 };
 
@@ -227,6 +221,83 @@ static int nw_hit_box_inv(NV o, NV d, NV inv, const float p0[4], const float p1[
   *t = closest;
   return face;
 }
+/* ---- triangle: "triangle (kTriangle) ... THE SPECIFICATION" ----------------
+ * Every product, sum and difference below is one float operation (the build
+ * keeps -ffp-contract=off); the three divisions of the ray constants and
+ * t = T / det are IEEE divisions. */
+static void nw_tri_verts(const nw_obj *ob, float v0[3], float v1[3], float v2[3]) {
+  v0[0] = ob->g0[0]; v0[1] = ob->g0[1]; v0[2] = ob->g0[2];
+  v1[0] = ob->g0[3]; v1[1] = ob->g1[0]; v1[2] = ob->g1[1];
+  v2[0] = ob->g1[2]; v2[1] = ob->g1[3]; v2[2] = ob->g2[0];
+}
+/* "never hit": the double cross product of the float vertices is the zero vector */
+static int nw_tri_collinear(const float v0[3], const float v1[3], const float v2[3]) {
+  double p[3], q[3];
+  for (int a = 0; a < 3; a++) {
+    p[a] = (double)v1[a] - (double)v0[a];
+    q[a] = (double)v2[a] - (double)v0[a];
+  }
+  const double cx = p[1] * q[2] - p[2] * q[1];
+  const double cy = p[2] * q[0] - p[0] * q[2];
+  const double cz = p[0] * q[1] - p[1] * q[0];
+  return cx == 0.0 && cy == 0.0 && cz == 0.0;
+}
+typedef struct nw_tri_fn {
+  float U, V, W, det, T;
+  int miss; /* the sign rule or det == 0 */
+} nw_tri_fn;
+static nw_tri_fn nw_tri_edges(NV o, NV d, const float v0[3], const float v1[3], const float v2[3]) {
+  const float dv[3] = {d.x, d.y, d.z}, ov[3] = {o.x, o.y, o.z};
+  /* ray constants */
+  int kz = 0;
+  if (fabsf(dv[1]) > fabsf(dv[kz])) kz = 1;
+  if (fabsf(dv[2]) > fabsf(dv[kz])) kz = 2;
+  int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
+  if (dv[kz] < 0.0f) {
+    const int sw = kx;
+    kx = ky;
+    ky = sw;
+  }
+  const float Sx = dv[kx] / dv[kz], Sy = dv[ky] / dv[kz], Sz = 1.0f / dv[kz];
+  /* test */
+  float A[3], B[3], C[3];
+  for (int a = 0; a < 3; a++) {
+    A[a] = v0[a] - ov[a];
+    B[a] = v1[a] - ov[a];
+    C[a] = v2[a] - ov[a];
+  }
+  const float Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz];
+  const float Bx = B[kx] - Sx * B[kz], By = B[ky] - Sy * B[kz];
+  const float Cx = C[kx] - Sx * C[kz], Cy = C[ky] - Sy * C[kz];
+  nw_tri_fn f;
+  f.U = Cx * By - Cy * Bx;
+  f.V = Ax * Cy - Ay * Cx;
+  f.W = Bx * Ay - By * Ax;
+  if (f.U == 0.0f || f.V == 0.0f || f.W == 0.0f) {
+    f.U = (float)((double)Cx * (double)By - (double)Cy * (double)Bx);
+    f.V = (float)((double)Ax * (double)Cy - (double)Ay * (double)Cx);
+    f.W = (float)((double)Bx * (double)Ay - (double)By * (double)Ax);
+  }
+  const int any_neg = f.U < 0.0f || f.V < 0.0f || f.W < 0.0f;
+  const int any_pos = f.U > 0.0f || f.V > 0.0f || f.W > 0.0f;
+  f.det = (f.U + f.V) + f.W;
+  f.miss = (any_neg && any_pos) || f.det == 0.0f;
+  const float Az = Sz * A[kz], Bz = Sz * B[kz], Cz = Sz * C[kz];
+  f.T = ((f.U * Az) + (f.V * Bz)) + (f.W * Cz);
+  return f;
+}
+static int nw_hit_triangle(const nw_obj *ob, NV o, NV d, float *t) {
+  float v0[3], v1[3], v2[3];
+  nw_tri_verts(ob, v0, v1, v2);
+  if (nw_tri_collinear(v0, v1, v2)) return 0;
+  const nw_tri_fn f = nw_tri_edges(o, d, v0, v1, v2);
+  if (f.miss) return 0;
+  const float tt = f.T / f.det;
+  if (!(tt >= 0.001f)) return 0;
+  *t = tt;
+  return 1;
+}
+
 static int nw_hit_boundary(const nw_obj *ob, NV o, NV d, float time, float tmin, float tmax, float *t) {
   const int bk = ob->aux & 255;
   if (bk == NW_SPHERE) return nw_hit_sphere(o, d, nv(ob->g0[0], ob->g0[1], ob->g0[2]), ob->g0[3], tmin, tmax, t);
@@ -275,8 +346,25 @@ static int nw_hit_object(const or_nw_scene *s, const nw_obj *ob, NV ow, NV dw, f
       if (k == NW_XZ) return nw_hit_rect_inv(1, 0, 2, o, d, inv, ob->g0[0], ob->g0[1], ob->g0[2], ob->g0[3], ob->g1[0], tmin, INFINITY, t);
       return nw_hit_rect_inv(0, 1, 2, o, d, inv, ob->g0[0], ob->g0[1], ob->g0[2], ob->g0[3], ob->g1[0], tmin, INFINITY, t);
     }
-    default: *face = nw_hit_box_inv(o, d, nv(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), ob->g0, ob->g1, tmin, INFINITY, t); return *face >= 0;
+    case NW_BOX: *face = nw_hit_box_inv(o, d, nv(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), ob->g0, ob->g1, tmin, INFINITY, t); return *face >= 0;
+    case NW_TRIANGLE: return nw_hit_triangle(ob, o, d, t);
+    default: return 0; /* not reached: nw_scene_known refuses the scene */
   }
+}
+/* 0 when every object's kind is one this file restates (the entry points
+ * refuse the scene otherwise: an unknown kind is never rendered as another) */
+static int nw_scene_known(const or_nw_scene *s) {
+  if (!s || s->n_obj < 0) return -1;
+  for (int32_t k = 0; k < s->n_obj; k++) {
+    const int32_t kind = nw_load(s, k).kind;
+    if (kind < 0 || kind >= NW_KINDS) return -1;
+  }
+  if (s->n_attr > 0) {
+    if (!s->attr || !s->attr_of_obj) return -1;
+    for (int32_t k = 0; k < s->n_obj; k++)
+      if (s->attr_of_obj[k] < -1 || s->attr_of_obj[k] >= s->n_attr) return -1;
+  }
+  return 0;
 }
 /* closest hit of a segment (DESIGN.md §9): media first (each hit marks
  * itself), then every other object by brute force over the list, skipping
@@ -416,7 +504,8 @@ typedef struct nw_rec {
   float u, v;
   int32_t mat;
 } nw_rec;
-static nw_rec nw_make_rec(const or_nw_scene *s, const nw_obj *ob, NV ow, NV dw, float time, float t, int face) {
+/* kk: the object's insertion index (finds a triangle's attribute record) */
+static nw_rec nw_make_rec(const or_nw_scene *s, int32_t kk, const nw_obj *ob, NV ow, NV dw, float time, float t, int face) {
   nw_rec r;
   r.mat = ob->mat;
   r.u = 0.0f;
@@ -442,6 +531,49 @@ static nw_rec nw_make_rec(const or_nw_scene *s, const nw_obj *ob, NV ow, NV dw, 
     const float inv_r = 1.0f / ob->g0[3];
     n = nv(inv_r * (p.x - c.x), inv_r * (p.y - c.y), inv_r * (p.z - c.z));
     if (need_uv) nw_sphere_uv(n, &r.u, &r.v);
+  } else if (ob->kind == NW_TRIANGLE) {
+    /* "record (make_rec)" of the triangle specification, then "Triangle
+     * attributes ... THE SPECIFICATION" for a triangle with a record */
+    float v0[3], v1[3], v2[3];
+    nw_tri_verts(ob, v0, v1, v2);
+    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
+    const float e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    const NV c = nv(e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]);
+    const float inv_len = 1.0f / sqrtf(ndot(c, c));
+    const NV ng = nv(c.x * inv_len, c.y * inv_len, c.z * inv_len);
+    n = ng;
+    const int32_t ai = s->n_attr > 0 ? s->attr_of_obj[kk] : -1;
+    if (ai >= 0) {
+      const float *ar = s->attr + 16 * (size_t)ai;
+      const float *n0 = ar, *n1 = ar + 3, *n2 = ar + 6, *t0 = ar + 9, *t1 = ar + 11, *t2 = ar + 13;
+      const int32_t flags = nw_ibits(ar[15]);
+      const nw_tri_fn f = nw_tri_edges(o, d, v0, v1, v2);
+      const float b0 = f.U / f.det, b1 = f.V / f.det, b2 = f.W / f.det;
+      if (flags & 1) {
+        NV ns = nv(fmaf(b2, n2[0], fmaf(b1, n1[0], b0 * n0[0])), fmaf(b2, n2[1], fmaf(b1, n1[1], b0 * n0[1])),
+                   fmaf(b2, n2[2], fmaf(b1, n1[2], b0 * n0[2])));
+        const float l2 = ndot(ns, ns);
+        if (l2 > 0.0f) {
+          const float inv_l = 1.0f / sqrtf(l2);
+          ns = nv(ns.x * inv_l, ns.y * inv_l, ns.z * inv_l);
+          const float a = ndot(d, ng), b = ndot(d, ns);
+          if ((a > 0.0f && b > 0.0f) || (a < 0.0f && b < 0.0f)) n = ns;
+        }
+      }
+      if (need_uv) {
+        if (flags & 2) {
+          r.u = fmaf(b2, t2[0], fmaf(b1, t1[0], b0 * t0[0]));
+          r.v = fmaf(b2, t2[1], fmaf(b1, t1[1], b0 * t0[1]));
+        } else {
+          r.u = b1;
+          r.v = b2;
+        }
+      }
+    } else if (need_uv) {
+      const nw_tri_fn f = nw_tri_edges(o, d, v0, v1, v2);
+      r.u = f.V / f.det;
+      r.v = f.W / f.det;
+    }
   } else {
     int kind = ob->kind;
     float a0, a1, b0, b1, x, y;
@@ -536,7 +668,8 @@ static int nw_scatter(const or_nw_scene *s, const nw_rec *rec, NV din, xo *g, NV
 
 /* ---- one camera sample: get_color main.cu:47-101 (forward form) ---------- */
 static NV nw_sample(const or_nw_scene *s, const int32_t *med_list, int32_t nmed, const fast_cam *k, float t0,
-                    float t1, int32_t W, int32_t H, int32_t max_depth, int32_t i, int32_t j, xo *g, int64_t *segs) {
+                    float t1, int32_t W, int32_t H, int32_t max_depth, int32_t i, int32_t j, xo *g, int64_t *segs,
+                    int64_t *won /* NW_KINDS + 1: segment winners by kind, then misses */) {
   float ju, jv;
   xo_pair(g, &ju, &jv);
   const float u = ((float)i + ju) / (float)W, v = ((float)j + jv) / (float)H;
@@ -550,9 +683,13 @@ static NV nw_sample(const or_nw_scene *s, const int32_t *med_list, int32_t nmed,
     float t;
     int face;
     const int32_t kk = nw_hit_world(s, med_list, nmed, o, d, time, seg_key, &t, &face);
-    if (kk < 0) return nv(T.x * s->bg[0], T.y * s->bg[1], T.z * s->bg[2]);
+    if (kk < 0) {
+      won[NW_KINDS]++;
+      return nv(T.x * s->bg[0], T.y * s->bg[1], T.z * s->bg[2]);
+    }
     const nw_obj ob = nw_load(s, kk);
-    const nw_rec rec = nw_make_rec(s, &ob, o, d, time, t, face);
+    won[ob.kind]++;
+    const nw_rec rec = nw_make_rec(s, kk, &ob, o, d, time, t, face);
     const float *m = s->mat + 4 * (size_t)rec.mat;
     if (nw_ibits(m[0]) == NWM_LIGHT) {
       const NV e = nw_tex_value(s, nw_ibits(m[1]), rec.u, rec.v, rec.p);
@@ -569,11 +706,14 @@ static NV nw_sample(const or_nw_scene *s, const int32_t *med_list, int32_t nmed,
 
 /* Rows row0 + r*row_step (r < nrows) of a W x H image: per-pixel sums over
  * spp samples (int64 fixed point, then float), same stream keys as the GPU.
- * Returns 0, or -1 on a bad argument; *segments = world.hit calls. */
-int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
-                     int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
-                     float *out, int64_t *segments) {
+ * Returns 0, or -1 on a bad argument or an object kind this file does not
+ * know; *segments = world.hit calls; winners (null, or NW_KINDS + 1 counts):
+ * over all those calls, the winners by object kind, then the misses. */
+int32_t or_nw_render_winners(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
+                             int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step,
+                             int32_t nrows, float *out, int64_t *segments, int64_t *winners) {
   if (!s || !c || W < 1 || H < 1 || spp < 1 || spp >= (1 << 24) || max_depth < 1 || nrows < 0) return -1;
+  if (nw_scene_known(s) != 0) return -1;
   fast_cam k;
   fast_build_cam(c, &k);
   int32_t med_list[64], nmed = 0;
@@ -584,7 +724,8 @@ int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, dou
     }
   const float t0 = (float)time0, t1 = (float)time1;
   int64_t total = (int64_t)nrows * W, segs = 0;
-#pragma omp parallel for schedule(dynamic, 4) reduction(+ : segs)
+  int64_t won[NW_KINDS + 1] = {0};
+#pragma omp parallel for schedule(dynamic, 4) reduction(+ : segs, won[:NW_KINDS + 1])
   for (int64_t q = 0; q < total; q++) {
     const int32_t r = (int32_t)(q / W), i = (int32_t)(q % W);
     const int32_t j = row0 + r * row_step;
@@ -594,7 +735,7 @@ int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, dou
       for (int32_t smp = 0; smp < spp; smp++) {
         xo g;
         xo_init(&g, seed, pixel, (uint32_t)smp);
-        const NV col = nw_sample(s, med_list, nmed, &k, t0, t1, W, H, max_depth, i, j, &g, &segs);
+        const NV col = nw_sample(s, med_list, nmed, &k, t0, t1, W, H, max_depth, i, j, &g, &segs, won);
         acc[0] += to_fixed(col.x);
         acc[1] += to_fixed(col.y);
         acc[2] += to_fixed(col.z);
@@ -603,7 +744,13 @@ int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, dou
     for (int ch = 0; ch < 3; ch++) out[3 * q + ch] = from_fixed(acc[ch]);
   }
   if (segments) *segments = segs;
+  if (winners) memcpy(winners, won, sizeof won);
   return 0;
+}
+int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
+                     int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
+                     float *out, int64_t *segments) {
+  return or_nw_render_winners(s, c, time0, time1, W, H, spp, max_depth, seed, row0, row_step, nrows, out, segments, 0);
 }
 
 /* Function hooks for tests: the transcendentals on n inputs
@@ -635,9 +782,11 @@ void or_nw_box_forms(int32_t n, const float *rays, const float *boxes, float *t_
   }
 }
 
-/* Debug mirror of rt_nw_debug_trace: the segments of one camera sample. */
+/* Debug mirror of rt_nw_debug_trace: the segments of one camera sample
+ * (their number; -1: an object kind this file does not know). */
 int32_t or_nw_trace(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
                     int32_t max_depth, uint64_t seed, int32_t i, int32_t j, int32_t smp, float *rec, int32_t cap) {
+  if (nw_scene_known(s) != 0) return -1;
   fast_cam k;
   fast_build_cam(c, &k);
   int32_t med_list[64], nmed = 0;
@@ -664,7 +813,7 @@ int32_t or_nw_trace(const or_nw_scene *s, const or_camera *c, double time0, doub
     r[11] = nw_fbits(face);
     if (kk < 0) break;
     const nw_obj ob = nw_load(s, kk);
-    const nw_rec rc = nw_make_rec(s, &ob, o, d, time, t, face);
+    const nw_rec rc = nw_make_rec(s, kk, &ob, o, d, time, t, face);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const float *m = s->mat + 4 * (size_t)rc.mat;
     NV at, nd;
@@ -678,12 +827,15 @@ int32_t or_nw_trace(const or_nw_scene *s, const or_camera *c, double time0, doub
 /* Closest hit of n given rays by brute force over the list (nw_hit_world):
  * the checker of rt_nw_debug_hits.  rays: {o.xyz, d.xyz, time, unused} per
  * ray; keys: the segments' medium keys (null: 0).  Out: insertion index
- * (-1: miss), t, box face (-1: none). */
-void or_nw_hits(const or_nw_scene *s, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
-                float *out_t, int32_t *out_face) {
+ * (-1: miss), t, box face (-1: none).  Returns 0, or -1 for an object kind
+ * this file does not know. */
+int32_t or_nw_hits(const or_nw_scene *s, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+                   float *out_t, int32_t *out_face) {
+  if (nw_scene_known(s) != 0) return -1;
   int32_t med_list[64], nmed = 0;
   for (int32_t q = 0; q < s->n_obj && nmed < 64; q++)
     if (nw_load(s, q).kind == NW_MEDIUM) med_list[nmed++] = q;
+#pragma omp parallel for schedule(static)
   for (int32_t i = 0; i < n; i++) {
     const float *r = rays + 8 * (size_t)i;
     NV o, d;
@@ -695,4 +847,41 @@ void or_nw_hits(const or_nw_scene *s, const float *rays, const uint64_t *keys, i
     out_t[i] = t;
     out_face[i] = face;
   }
+  return 0;
+}
+
+/* Mirror of rt_nw_debug_records: the closest hit of each ray as or_nw_hits
+ * finds it, then the record a render makes of it.  Out per ray: insertion
+ * index, t, {p.xyz, n.xyz, u, v} (world space) and the material; a miss writes
+ * index -1 and zeros.  Returns 0, or -1 for an unknown object kind. */
+int32_t or_nw_records(const or_nw_scene *s, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+                      float *out_t, float *out_pnuv, int32_t *out_mat) {
+  if (nw_scene_known(s) != 0) return -1;
+  int32_t med_list[64], nmed = 0;
+  for (int32_t q = 0; q < s->n_obj && nmed < 64; q++)
+    if (nw_load(s, q).kind == NW_MEDIUM) med_list[nmed++] = q;
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; i++) {
+    const float *r = rays + 8 * (size_t)i;
+    float *q = out_pnuv + 8 * (size_t)i;
+    const NV o = nv(r[0], r[1], r[2]), d = nv(r[3], r[4], r[5]);
+    float t;
+    int face;
+    const int32_t kk = nw_hit_world(s, med_list, nmed, o, d, r[6], keys ? keys[i] : 0ull, &t, &face);
+    out_id[i] = kk;
+    if (kk < 0) {
+      out_t[i] = 0.0f;
+      out_mat[i] = 0;
+      for (int c = 0; c < 8; c++) q[c] = 0.0f;
+      continue;
+    }
+    const nw_obj ob = nw_load(s, kk);
+    const nw_rec rc = nw_make_rec(s, kk, &ob, o, d, r[6], t, face);
+    out_t[i] = t;
+    out_mat[i] = rc.mat;
+    q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
+    q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
+    q[6] = rc.u; q[7] = rc.v;
+  }
+  return 0;
 }

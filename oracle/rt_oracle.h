@@ -108,6 +108,36 @@ int64_t or_fast_segments(const or_scene *s, const or_camera *c, int32_t W, int32
                          int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0,
                          int32_t row_step, int32_t nrows);
 
+/* ---- Next-Week restatement (rt_nw_oracle.inc): the flattened scene of
+ * rt_nw_scene_flat / rt_nw_scene_flat_attr and the entry points the tests use */
+typedef struct or_nw_scene {
+  int32_t n_obj, n_inst;
+  const float *obj;       /* 16 per object: g0[4] g1[4] g2[4] kind mat inst aux (int bits) */
+  const float *inst;      /* 8 per instance: c s ox oy oz flags(int bits) 0 0 */
+  const float *mat;       /* 4 per material: kind tex (int bits) fuzz ir */
+  const float *tex;       /* 8 per texture: kind a b 0 (int bits) r g b scale */
+  const float *perlin_vec;    /* 256 * 4 per perlin */
+  const int32_t *perlin_perm; /* 768 per perlin */
+  const int32_t *image_desc;  /* 4 per image: offset w h 0 */
+  const uint8_t *image_px;
+  float bg[3];
+  int32_t n_attr;             /* triangle attribute records (0: none; then the two below may be null) */
+  const float *attr;          /* 16 per record: n0[3] n1[3] n2[3] uv0[2] uv1[2] uv2[2] flags (int bits) */
+  const int32_t *attr_of_obj; /* per object: its record, -1 none */
+} or_nw_scene;
+int32_t or_nw_render(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
+                     int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
+                     float *out, int64_t *segments);
+int32_t or_nw_render_winners(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
+                             int32_t spp, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step,
+                             int32_t nrows, float *out, int64_t *segments, int64_t *winners /* 9, or null */);
+int32_t or_nw_trace(const or_nw_scene *s, const or_camera *c, double time0, double time1, int32_t W, int32_t H,
+                    int32_t max_depth, uint64_t seed, int32_t i, int32_t j, int32_t smp, float *rec, int32_t cap);
+int32_t or_nw_hits(const or_nw_scene *s, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+                   float *out_t, int32_t *out_face);
+int32_t or_nw_records(const or_nw_scene *s, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+                      float *out_t, float *out_pnuv, int32_t *out_mat);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,7 +190,12 @@ def load_camera_txt(path):
 class OrNwScene(C.Structure):
     _fields_ = [("n_obj", C.c_int32), ("n_inst", C.c_int32)] + [
         (nm, _fp) for nm in ("obj", "inst", "mat", "tex", "perlin_vec")
-    ] + [("perlin_perm", _ip), ("image_desc", _ip), ("image_px", C.POINTER(C.c_uint8)), ("bg", C.c_float * 3)]
+    ] + [("perlin_perm", _ip), ("image_desc", _ip), ("image_px", C.POINTER(C.c_uint8)), ("bg", C.c_float * 3),
+         ("n_attr", C.c_int32), ("attr", _fp), ("attr_of_obj", _ip)]
+
+
+NW_KIND_NAMES = ("sphere", "moving_sphere", "rect_xy", "rect_xz", "rect_yz", "box", "medium", "triangle")
+_u64p = C.POINTER(C.c_uint64)
 
 
 def _nw_bind():
@@ -199,13 +204,23 @@ def _nw_bind():
         L.or_nw_render.argtypes = [C.POINTER(OrNwScene), C.POINTER(OrCamera), C.c_double, C.c_double] + [C.c_int32] * 4 + [
             C.c_uint64] + [C.c_int32] * 3 + [_fp, _lp]
         L.or_nw_render.restype = C.c_int32
+        L.or_nw_render_winners.argtypes = L.or_nw_render.argtypes + [_lp]
+        L.or_nw_render_winners.restype = C.c_int32
+        L.or_nw_trace.argtypes = [C.POINTER(OrNwScene), C.POINTER(OrCamera), C.c_double, C.c_double] + [C.c_int32] * 3 + [
+            C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32]
+        L.or_nw_trace.restype = C.c_int32
+        L.or_nw_hits.argtypes = [C.POINTER(OrNwScene), _fp, _u64p, C.c_int32, _ip, _fp, _ip]
+        L.or_nw_hits.restype = C.c_int32
+        L.or_nw_records.argtypes = [C.POINTER(OrNwScene), _fp, _u64p, C.c_int32, _ip, _fp, _fp, _ip]
+        L.or_nw_records.restype = C.c_int32
         L.or_nw_math.argtypes = [C.c_int32, C.c_int32, _fp, _fp]
         L._nw_bound = True
     return L
 
 
-def nw_scene(flat):
-    """OrNwScene over the arrays of nextweek.Scene.flat() (kept alive on the struct)."""
+def nw_scene(flat, flat_attr=None):
+    """OrNwScene over the arrays of nextweek.Scene.flat() and, when the scene
+    has triangle attribute records, Scene.flat_attr() (kept alive on the struct)."""
     keep = {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in flat.items()}
     for k in ("obj", "inst", "mat", "tex", "perlin_vec", "perlin_perm", "image_desc", "image_px"):
         if keep[k].size == 0:
@@ -220,23 +235,37 @@ def nw_scene(flat):
     s.image_px = keep["image_px"].ctypes.data_as(C.POINTER(C.c_uint8))
     for c in range(3):
         s.bg[c] = float(flat["background"][c])
+    s.n_attr = 0
+    if flat_attr is not None and np.asarray(flat_attr["attr"]).size > 0:
+        keep["attr"] = np.ascontiguousarray(flat_attr["attr"], np.float32).reshape(-1, 16)
+        keep["attr_of_obj"] = np.ascontiguousarray(flat_attr["attr_of_obj"], np.int32)
+        if keep["attr_of_obj"].size != s.n_obj or keep["attr_of_obj"].max(initial=-1) >= len(keep["attr"]):
+            raise ValueError("nw_scene: attr_of_obj does not fit the scene")
+        s.n_attr = len(keep["attr"])
+        s.attr = keep["attr"].ctypes.data_as(_fp)
+        s.attr_of_obj = keep["attr_of_obj"].ctypes.data_as(_ip)
     s._keep = keep
     return s
 
 
-def nw_render(flat, nwcam, W, H, spp, depth, seed, row0=0, row_step=1, nrows=None):
-    """Oracle image (sums) + world.hit count for rows row0 + r*row_step of a W x H Next-Week render."""
+def nw_render(flat, nwcam, W, H, spp, depth, seed, row0=0, row_step=1, nrows=None, flat_attr=None, winners=False):
+    """Oracle image (sums) + world.hit count for rows row0 + r*row_step of a W x H Next-Week render.
+    winners: also {kind name: segments it won, ..., "miss": segments that hit nothing}."""
     L = _nw_bind()
     nrows = H if nrows is None else nrows
-    s = nw_scene(flat)
+    s = nw_scene(flat, flat_attr)
     cam = OrCamera()
     C.memmove(C.byref(cam), C.byref(nwcam.cam), C.sizeof(cam))
     out = np.zeros(nrows * W * 3, np.float32)
     segs = C.c_int64()
-    rc = L.or_nw_render(C.byref(s), C.byref(cam), nwcam.time0, nwcam.time1, W, H, spp, depth, seed, row0, row_step,
-                        nrows, out.ctypes.data_as(_fp), C.byref(segs))
+    won = np.zeros(len(NW_KIND_NAMES) + 1, np.int64)
+    rc = L.or_nw_render_winners(C.byref(s), C.byref(cam), nwcam.time0, nwcam.time1, W, H, spp, depth, seed, row0,
+                                row_step, nrows, out.ctypes.data_as(_fp), C.byref(segs), won.ctypes.data_as(_lp))
     if rc != 0:
-        raise ValueError("or_nw_render failed")
+        raise ValueError("or_nw_render failed (a bad argument, or an object kind the oracle does not know)")
+    if winners:
+        assert won.sum() == segs.value
+        return out.reshape(nrows, W, 3), segs.value, dict(zip(NW_KIND_NAMES + ("miss",), won.tolist()))
     return out.reshape(nrows, W, 3), segs.value
 
 
@@ -264,37 +293,57 @@ def nw_box_forms(rays, boxes):
     return td, fd, ti, fi
 
 
-def nw_trace(flat, nwcam, W, H, depth, seed, i, j, smp, cap=64):
+def nw_trace(flat, nwcam, W, H, depth, seed, i, j, smp, cap=64, flat_attr=None):
     """Oracle mirror of NwRenderer.debug_trace."""
     L = _nw_bind()
-    L.or_nw_trace.argtypes = [C.POINTER(OrNwScene), C.POINTER(OrCamera), C.c_double, C.c_double] + [C.c_int32] * 3 + [
-        C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32]
-    L.or_nw_trace.restype = C.c_int32
-    s = nw_scene(flat)
+    s = nw_scene(flat, flat_attr)
     cam = OrCamera()
     C.memmove(C.byref(cam), C.byref(nwcam.cam), C.sizeof(cam))
     rec = np.zeros(12 * cap, np.float32)
     n = L.or_nw_trace(C.byref(s), C.byref(cam), nwcam.time0, nwcam.time1, W, H, depth, seed, i, j, smp,
                       rec.ctypes.data_as(_fp), cap)
+    if n < 0:
+        raise ValueError("or_nw_trace failed (an object kind the oracle does not know)")
     out = rec[: 12 * n].reshape(-1, 12).copy()
     return out[:, [0, 1, 2, 3, 4, 5, 6, 8, 9, 10]], out[:, [7, 11]].view(np.int32)
 
 
-def nw_hits(flat, rays, keys=None):
+def _nw_rays(rays, keys):
+    r = np.zeros((len(rays), 8), np.float32)
+    r[:, :7] = np.asarray(rays)[:, :7]
+    k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+    return r, k, (None if k is None else k.ctypes.data_as(_u64p))
+
+
+def nw_hits(flat, rays, keys=None, flat_attr=None):
     """Oracle mirror of NwRenderer.debug_hits: the brute-force closest hit of
     each ray (rows o.xyz, d.xyz, time): (insertion index or -1, t, box face)."""
     L = _nw_bind()
-    L.or_nw_hits.argtypes = [C.POINTER(OrNwScene), _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _ip]
-    L.or_nw_hits.restype = None
-    s = nw_scene(flat)
+    s = nw_scene(flat, flat_attr)
     n = len(rays)
-    r = np.zeros((n, 8), np.float32)
-    r[:, :7] = rays
-    k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+    r, k, kp = _nw_rays(rays, keys)
     idx, t, face = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32)
-    L.or_nw_hits(C.byref(s), r.ctypes.data_as(_fp), None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), n,
-                 idx.ctypes.data_as(_ip), t.ctypes.data_as(_fp), face.ctypes.data_as(_ip))
+    rc = L.or_nw_hits(C.byref(s), r.ctypes.data_as(_fp), kp, n, idx.ctypes.data_as(_ip), t.ctypes.data_as(_fp),
+                      face.ctypes.data_as(_ip))
+    if rc != 0:
+        raise ValueError("or_nw_hits failed (an object kind the oracle does not know)")
     return idx, t, face
+
+
+def nw_records(flat, rays, keys=None, flat_attr=None):
+    """Oracle mirror of NwRenderer.debug_records: (insertion index or -1, t,
+    rows p.xyz n.xyz u v, material); a miss is -1 and zeros."""
+    L = _nw_bind()
+    s = nw_scene(flat, flat_attr)
+    n = len(rays)
+    r, k, kp = _nw_rays(rays, keys)
+    idx, t = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    rec, mat = np.zeros((n, 8), np.float32), np.zeros(n, np.int32)
+    rc = L.or_nw_records(C.byref(s), r.ctypes.data_as(_fp), kp, n, idx.ctypes.data_as(_ip), t.ctypes.data_as(_fp),
+                         rec.ctypes.data_as(_fp), mat.ctypes.data_as(_ip))
+    if rc != 0:
+        raise ValueError("or_nw_records failed (an object kind the oracle does not know)")
+    return idx, t, rec, mat
 
 
 def row_mean_z(frame_rows, S, a, b, s_ab):
