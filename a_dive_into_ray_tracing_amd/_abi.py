@@ -142,6 +142,13 @@ SIGNATURES = {
                                                C.c_int32, C.c_int32, C.c_double, C.POINTER(RtNwCamera), _ip]),
     "rt_nw_shared": (C.c_int, [C.c_void_p, C.c_int32]),
     "rt_nw_scene_instancing_stats": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_move": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_double, C.c_double]),
+    "rt_nw_scene_flat_at": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(RtNwFlat)]),
+    "rt_nw_scene_motion_stats": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_scene_obj_stage_moving": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
+                                               C.c_int32, C.c_int32, _dp, C.c_double, C.POINTER(RtNwCamera), _ip]),
+    "rt_nw_ctx_scene_tri": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_debug_trace_t": (C.c_int, [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 3 + [C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32, _ip, _fp]),
     "rt_nw_debug_records": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _fp, _ip]),
     "rt_nw_constant_medium": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     "rt_nw_medium_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -101,6 +101,19 @@ template <bool S> constexpr int persist_waves() { return S ? RTMI_NW_SIMPLE_WAVE
 #ifndef RTMI_NW_INST_PER_EU
 #define RTMI_NW_INST_PER_EU 8
 #endif
+// Scenes with a moving placement (TRI = 4: the same walk, the placement's
+// offset formed at the ray's time on entering it).  TRI = 3's choice does not
+// carry over: compiled for 8 waves per SIMD (64 VGPRs, 191-229 spilled) the
+// persistent kernels render the fields of profiles/motion/README.md in 74.0 /
+// 110.7 / 123.9 / 186.6 ms (every placement moving; 65.4 / 101.8 / 109.0 / 172.4
+// with every placement under a move at rest, against 49.9 / 74.5 / 84.5 / 123.9
+// of the static TRI = 3 build of the same fields), compiled for 4 (128 VGPRs,
+// no scratch, one 16-wave block per CU) in 57.9 / 88.1 / 111.1 / 170.0 ms (at
+// rest 48.4 / 81.1 / 93.5 / 156.9).  Why the 8-wave build loses that much to
+// TRI = 3's at the same size and spill count was not found.
+#ifndef RTMI_NW_MOVE_PER_EU
+#define RTMI_NW_MOVE_PER_EU 4
+#endif
 constexpr size_t kCuLds = 160 * 1024;
 constexpr size_t kPStaticLds = (sizeof(unsigned long long) * 3 * 64 * kPWaves + 23 * sizeof(float) + 255) / 256 * 256;
 constexpr size_t kPTwoBlockBudget = kCuLds / 2 - kPStaticLds;
@@ -266,8 +279,8 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
       const uint64_t seg_key = !S && sc.has_media ? rng.next() : 0ull;
       float t;
       int face;
-      int32_t sub = -1;  // the winner's pool slot when it is a placement's triangle (TRI = 3)
-      const int32_t k = TRI == 3 ? hit_world_nw_inst<LDS_NODES, LDS_OBJS>(sc, o, d, time, seg_key, t, face, sub, &cnt)
+      int32_t sub = -1;  // the winner's pool slot when it is a placement's triangle (TRI = 3, 4)
+      const int32_t k = TRI >= 3 ? hit_world_nw_inst<LDS_NODES, LDS_OBJS, TRI == 4>(sc, o, d, time, seg_key, t, face, sub, &cnt)
                         : GRID   ? hit_world_nw_grid<S, TRI>(sc, o, d, time, seg_key, t, face, &cnt)
                                  : hit_world_nw<LDS_NODES, LDS_OBJS, TRI>(sc, o, d, time, seg_key, t, face, &cnt);
 #if RTMI_NW_PHASES
@@ -277,7 +290,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
         col = mk(T.x * sc.bg[0], T.y * sc.bg[1], T.z * sc.bg[2]);
         done = true;
       } else {
-        const Rec rec = TRI == 3 && k < sc.nobj ? make_rec_inst(sc, k, sub, o, d, time, t, face)
+        const Rec rec = TRI >= 3 && k < sc.nobj ? make_rec_inst<TRI == 4>(sc, k, sub, o, d, time, t, face)
                         : S || k < sc.nobj      ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face, attr_view_of(sc), k)
                                                 : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
         const Mat m = sc.mat[rec.mat];
@@ -356,7 +369,8 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
 
 // TRI (last parameter of both kernels): the scene holds no triangle (0), triangles (1), triangles with
 // attribute records (2; hit_object, make_rec), placements of shared meshes (3; hit_world_nw_inst: BVH
-// shapes only, such a scene has no uniform grid)
+// shapes only, such a scene has no uniform grid), placements of which some move (4; the same walk with
+// the moving placements' offsets formed at the ray's time)
 template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, int TRI = 0>
 __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, unsigned long long *__restrict__ accum,
                                                              float *__restrict__ out,
@@ -379,7 +393,7 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
 template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
-__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
+__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI == 4 ? RTMI_NW_MOVE_PER_EU : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
                                                                   unsigned long long *__restrict__ segments,
@@ -405,8 +419,8 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
 // i, j, sample s): per segment o.xyz, d.xyz, t, winner insertion index (as
 // float bits) — the oracle's or_nw_trace records the same.
 // has_attr: the scene has triangle attribute records (attr_view_of).
-// INST: a scene with placements of shared meshes (the two-level walk).
-template <bool INST>
+// INST: a scene with placements of shared meshes (the two-level walk); 2: some of them move.
+template <int INST>
 __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i, int j, int s, float *rec, int cap, int *n_out,
                                            int has_attr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -427,7 +441,7 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
     float t;
     int face;
     int32_t sub = -1;
-    const int32_t k = INST ? hit_world_nw_inst<false, false>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
+    const int32_t k = INST ? hit_world_nw_inst<false, false, INST == 2>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
                            : hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
@@ -436,7 +450,7 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
     r[11] = __int_as_float(face);
     if (k < 0) break;
     const Rec rc = k >= sc.nobj ? make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time)
-                   : INST       ? make_rec_inst(sc, k, sub, o, d, time, t, face)
+                   : INST       ? make_rec_inst<INST == 2>(sc, k, sub, o, d, time, t, face)
                                 : make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
@@ -448,10 +462,24 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
   *n_out = n;
 }
 __global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
-  trace_body<false>(sc, a, i, j, s, rec, cap, n_out, has_attr);
+  trace_body<0>(sc, a, i, j, s, rec, cap, n_out, has_attr);
 }
 __global__ void trace_inst_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
-  trace_body<true>(sc, a, i, j, s, rec, cap, n_out, 0);
+  trace_body<1>(sc, a, i, j, s, rec, cap, n_out, 0);
+}
+__global__ void trace_move_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
+  trace_body<2>(sc, a, i, j, s, rec, cap, n_out, 0);
+}
+// The ray time of that camera sample (rt_nw_debug_trace_t): trace_body's draws up to the time
+__global__ void trace_time_kernel(Args a, int i, int j, int s, float *time_out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  Xoro rng;
+  rng.init(a.seed, uint64_t(j) * uint64_t(a.W) + uint64_t(i), uint32_t(s));
+  float ju, jv;
+  rng.pair(ju, jv);
+  V o, d;
+  get_ray<true, float>(a.cam, (float(i) + ju) / float(a.W), (float(j) + jv) / float(a.H), rng, o, d);
+  *time_out = __builtin_fmaf(rng.uni(), a.time1 - a.time0, a.time0);
 }
 
 __global__ void finalize_kernel(const unsigned long long *__restrict__ acc, float *__restrict__ out, size_t n) {
@@ -484,10 +512,11 @@ __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *_
 }
 // ... of a scene with placements of shared meshes: the two-level walk, nodes
 // and records in global memory
-__global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const float *__restrict__ rays,
-                                                              const unsigned long long *__restrict__ keys, int32_t n,
-                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                              int32_t *__restrict__ out_face) {
+template <bool MOVE>
+__device__ __forceinline__ void debug_hits_inst_body(const View &sc, const float *__restrict__ rays,
+                                                     const unsigned long long *__restrict__ keys, int32_t n,
+                                                     int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                     int32_t *__restrict__ out_face) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float *r = rays + 8 * size_t(i);
@@ -496,10 +525,23 @@ __global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const flo
   float t;
   int face;
   int32_t sub;
-  const int32_t k = hit_world_nw_inst<false, false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
+  const int32_t k = hit_world_nw_inst<false, false, MOVE>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
   out_id[i] = k < 0 ? -1 : k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_face[i] = face;
+}
+__global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const float *__restrict__ rays,
+                                                              const unsigned long long *__restrict__ keys, int32_t n,
+                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                              int32_t *__restrict__ out_face) {
+  debug_hits_inst_body<false>(sc, rays, keys, n, out_id, out_t, out_face);
+}
+// ... some of whose placements move (TRI = 4)
+__global__ __launch_bounds__(256) void debug_hits_move_kernel(View sc, const float *__restrict__ rays,
+                                                              const unsigned long long *__restrict__ keys, int32_t n,
+                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                              int32_t *__restrict__ out_face) {
+  debug_hits_inst_body<true>(sc, rays, keys, n, out_id, out_t, out_face);
 }
 
 // The hit record of n given rays (validation: rt_nw_debug_records): the
@@ -542,10 +584,11 @@ __global__ __launch_bounds__(256) void debug_records_kernel(View sc, const float
   q[6] = rc.u; q[7] = rc.v;
 }
 // ... of a scene with placements of shared meshes (as debug_hits_inst_kernel)
-__global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const float *__restrict__ rays,
-                                                                 const unsigned long long *__restrict__ keys, int32_t n,
-                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
+template <bool MOVE>
+__device__ __forceinline__ void debug_records_inst_body(const View &sc, const float *__restrict__ rays,
+                                                        const unsigned long long *__restrict__ keys, int32_t n,
+                                                        int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                        float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float *r = rays + 8 * size_t(i);
@@ -554,7 +597,7 @@ __global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const 
   float t;
   int face;
   int32_t sub;
-  const int32_t k = hit_world_nw_inst<false, false>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
+  const int32_t k = hit_world_nw_inst<false, false, MOVE>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
   float *q = out_pnuv + 8 * size_t(i);
   if (k < 0) {
     out_id[i] = -1;
@@ -563,13 +606,26 @@ __global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const 
     for (int c = 0; c < 8; ++c) q[c] = 0.0f;
     return;
   }
-  const Rec rc = k < sc.nobj ? make_rec_inst(sc, k, sub, o, d, r[6], t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
+  const Rec rc = k < sc.nobj ? make_rec_inst<MOVE>(sc, k, sub, o, d, r[6], t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
   out_id[i] = k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
   out_t[i] = t;
   out_mat[i] = rc.mat;
   q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
   q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
   q[6] = rc.u; q[7] = rc.v;
+}
+__global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const float *__restrict__ rays,
+                                                                 const unsigned long long *__restrict__ keys, int32_t n,
+                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
+  debug_records_inst_body<false>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
+}
+// ... some of whose placements move (TRI = 4)
+__global__ __launch_bounds__(256) void debug_records_move_kernel(View sc, const float *__restrict__ rays,
+                                                                 const unsigned long long *__restrict__ keys, int32_t n,
+                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
+  debug_records_inst_body<true>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
 }
 
 }  // namespace nw
@@ -615,7 +671,8 @@ struct rt_nw_ctx {
   float bg[3] = {0.f, 0.f, 0.f};
   int32_t has_media = 0;
   int32_t has_tri = 0;  // the kernels' TRI: 0 no triangle, 1 triangles, 2 triangles with attribute records,
-                        // 3 placements of shared meshes (nobj, nnodes: the top level's)
+                        // 3 placements of shared meshes (nobj, nnodes: the top level's), 4 placements of which
+                        // at least one moves (rt_nw_move)
   int32_t npool = 0, nbot = 0;  // TRI = 3: pool slots behind obj[nobj], bottom-level nodes behind nodes[2 * nnodes]
   int32_t nattr = 0;    // attribute records behind obj[nobj] (their locator behind obj_id[nobj]); 0: neither exists
   unsigned long long *accum = nullptr;
@@ -771,10 +828,27 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   const int32_t nt = int32_t(ds.tex.size()), nm = int32_t(ds.mat.size()), ni = int32_t(ds.inst.size());
   const int32_t np = int32_t(ds.perlin_perm.size() / (3 * kPerlinN)), nim = int32_t(ds.image.size());
   const bool two_level = !ds.place_mesh.empty();
-  for (const Obj &o : ds.obj)
+  int32_t n_moving = 0;
+  for (const Obj &o : ds.obj) {
     if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere ||
-        (o.kind > kBox && o.kind != kTriangle && !(two_level && o.kind == kInstance)) || o.aux < 0 || o.aux > int32_t(ds.med.size()))
+        (o.kind > kBox && o.kind != kTriangle && !(two_level && o.kind == kInstance)) || o.aux < 0 ||
+        o.aux > (o.kind == kInstance ? 1 : int32_t(ds.med.size())))
       return set_error(RT_EINVAL, "rt_nw: object with bad material/instance/kind");
+    if (o.kind != kInstance) continue;
+    // a placement's motion words (rtmi_nw_types.h kInstance): all zero, or a
+    // moving placement's — an Inst with the translation flag, o1 and two times
+    // the walk can divide by
+    if (o.aux == 0) {
+      if (o.g1[1] != 0.f || o.g1[2] != 0.f || o.g1[3] != 0.f || o.g2[0] != 0.f || o.g2[1] != 0.f)
+        return set_error(RT_EINVAL, "rt_nw: static placement with motion words");
+      continue;
+    }
+    ++n_moving;
+    if (o.inst < 0 || !(ds.inst[size_t(o.inst)].flags & 2) || !std::isfinite(o.g1[1]) || !std::isfinite(o.g1[2]) ||
+        !std::isfinite(o.g1[3]) || !std::isfinite(o.g2[0]) || !std::isfinite(o.g2[1]) || o.g2[0] == o.g2[1])
+      return set_error(RT_EINVAL, "rt_nw: bad motion in a placement record");
+  }
+  if (n_moving != ds.n_moving) return set_error(RT_EINVAL, "rt_nw: moving placement records do not match the count");
   // shared meshes: every link the two-level walk follows (rtmi_nw_path.h hit_world_nw_inst)
   const size_t npool = ds.pool.size(), nbot = ds.bnodes.size();
   if (!two_level && (npool || nbot || !ds.mesh.empty())) return set_error(RT_EINVAL, "rt_nw: shared pool without a placement");
@@ -893,6 +967,7 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
     }
     q.ka = o.kind | (o.aux << 8);
     q.mat = o.mat;
+    if (o.kind == kInstance) std::memcpy(&q.mat, &o.g2[1], 4);  // time0 of a moving placement (else zero bits)
     q.t1 = o.g2[0];
     q.inst = o.inst;
   }
@@ -960,7 +1035,7 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   for (const Obj &o : ds.obj) ctx->has_tri |= o.kind == kTriangle ? 1 : 0;
   ctx->nattr = int32_t(nattr);
   if (nattr) ctx->has_tri = 2;
-  if (two_level) ctx->has_tri = 3;
+  if (two_level) ctx->has_tri = ds.n_moving > 0 ? 4 : 3;
   ctx->npool = int32_t(npool);
   ctx->nbot = int32_t(nbot);
   bool simple = ds.med.empty();
@@ -1077,7 +1152,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   // objects staged beside the nodes only when two blocks still fit a CU (or
   // when one block per CU is all the nodes allow anyway)
   // (the two-level kernels below 8 waves per SIMD run one block per CU whatever they stage)
-  const bool one_block = ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8;
+  const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8);
   const bool p_objs = RTMI_NW_LDS_OBJS && persist &&
                       (node_bytes + obj_bytes <= kPTwoBlockBudget ||
                        ((one_block || node_bytes > kPTwoBlockBudget) && node_bytes + obj_bytes <= kPLdsBudget));
@@ -1092,7 +1167,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   // (persistent) how many of its blocks stay resident with those bytes
   auto kernel_of = [&](auto tri) -> const void * {
     constexpr int T = decltype(tri)::value;
-    if constexpr (T == 3)  // (BVH shapes only)
+    if constexpr (T >= 3)  // (BVH shapes only)
       return persist && p_objs ? (const void *)render_persistent<true, true, false, false, T>
              : persist         ? (const void *)render_persistent<true, false, false, false, T>
              : lds_objs        ? (const void *)render_kernel<true, true, true, false, T>
@@ -1112,8 +1187,10 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   using Tri1 = std::integral_constant<int, 1>;
   using Tri2 = std::integral_constant<int, 2>;
   using Tri3 = std::integral_constant<int, 3>;
-  if (ctx->has_tri == 3 && use_grid) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
-  const void *kfn = ctx->has_tri == 3   ? kernel_of(Tri3{})
+  using Tri4 = std::integral_constant<int, 4>;
+  if (ctx->has_tri >= 3 && use_grid) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
+  const void *kfn = ctx->has_tri == 4   ? kernel_of(Tri4{})
+                    : ctx->has_tri == 3 ? kernel_of(Tri3{})
                     : ctx->has_tri == 2 ? kernel_of(Tri2{})
                     : ctx->has_tri      ? kernel_of(Tri1{})
                                         : kernel_of(Tri0{});
@@ -1159,7 +1236,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   auto launch_t = [&](auto chunked, auto tri) {
     constexpr bool C = decltype(chunked)::value;
     constexpr int T = decltype(tri)::value;
-    if constexpr (T != 3) {  // (a scene with placements has no grid)
+    if constexpr (T < 3) {  // (a scene with placements has no grid)
       if (simple) {
         hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
         return;
@@ -1185,7 +1262,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
       hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
   };
   auto launch = [&](auto chunked) {
-    if (ctx->has_tri == 3) launch_t(chunked, Tri3{});
+    if (ctx->has_tri == 4) launch_t(chunked, Tri4{});
+    else if (ctx->has_tri == 3) launch_t(chunked, Tri3{});
     else if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
     else if (ctx->has_tri) launch_t(chunked, Tri1{});
     else launch_t(chunked, Tri0{});
@@ -1242,7 +1320,9 @@ RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   int *d_n = nullptr;
   HIP_TRY(hipMalloc(&d_rec, size_t(cap) * 12 * sizeof(float)));
   HIP_TRY(hipMalloc(&d_n, sizeof(int)));
-  if (ctx->has_tri == 3)
+  if (ctx->has_tri == 4)
+    hipLaunchKernelGGL(trace_move_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
+  else if (ctx->has_tri == 3)
     hipLaunchKernelGGL(trace_inst_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
   else
     hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n,
@@ -1253,6 +1333,35 @@ RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   (void)hipFree(d_rec);
   (void)hipFree(d_n);
   if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_trace: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_debug_trace_t(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t max_depth,
+                                    uint64_t seed, int32_t i, int32_t j, int32_t s, float *rec, int32_t cap, int32_t *n,
+                                    float *time) {
+  if (!time) return set_error(RT_EINVAL, "rt_nw_debug_trace_t: null time");
+  if (int rc = rt_nw_debug_trace(ctx, cam, W, H, max_depth, seed, i, j, s, rec, cap, n)) return rc;
+  Guard g(ctx->device);
+  Args a{};
+  a.cam = camf(cam->cam);
+  a.time0 = float(cam->time0);
+  a.time1 = float(cam->time1);
+  a.W = W;
+  a.H = H;
+  a.seed = seed;
+  float *d_time = nullptr;
+  HIP_TRY(hipMalloc(&d_time, sizeof(float)));
+  hipLaunchKernelGGL(trace_time_kernel, dim3(1), dim3(64), 0, ctx->stream, a, i, j, s, d_time);
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(time, d_time, sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(d_time);
+  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_trace_t: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_ctx_scene_tri(rt_nw_ctx *ctx, int32_t *tri) {
+  if (!ctx || !tri) return set_error(RT_EINVAL, "null");
+  *tri = ctx->has_tri;
   return RT_OK;
 }
 
@@ -1278,7 +1387,9 @@ RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64
   if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
-    if (ctx->has_tri == 3)
+    if (ctx->has_tri == 4)
+      hipLaunchKernelGGL(debug_hits_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
+    else if (ctx->has_tri == 3)
       hipLaunchKernelGGL(debug_hits_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
     else if (grid)
       hipLaunchKernelGGL(debug_hits_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id,
@@ -1325,7 +1436,10 @@ RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uin
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
     const int has_attr = ctx->nattr > 0 ? 1 : 0;
-    if (ctx->has_tri == 3)
+    if (ctx->has_tri == 4)
+      hipLaunchKernelGGL(debug_records_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
+                         d_mat);
+    else if (ctx->has_tri == 3)
       hipLaunchKernelGGL(debug_records_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
                          d_mat);
     else if (grid)

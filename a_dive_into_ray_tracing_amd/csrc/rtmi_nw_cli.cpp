@@ -8,7 +8,8 @@
 //                  [--spp S] [--depth D] [--seed N] [--texture FILE.ppm]
 //                  [--out FILE|-] [--p6] [--rtl]
 //   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
-//                  [--obj-texture FILE.ppm] [--obj-copies N] [--width W] ...
+//                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--width W] ...
+//   either form: [--shutter T0,T1]
 //
 // --obj (exclusive with --scene) renders a Wavefront OBJ mesh
 // (rt_nw_scene_obj_stage): scaled and centred into the box [-1, 1] x [0, 2] x
@@ -20,6 +21,10 @@
 // the file's vt (lambertian or metal); none of the three is valid with --scene.
 // --obj-copies N stages the model as one shared mesh (rt_nw_shared) placed
 // N x N times on the ground (rt_nw_scene_obj_stage_copies; 1: the stage above).
+// --obj-move DX,DY,DZ makes every placement move by that vector over the times
+// [0, 1] (rt_nw_move, rt_nw_scene_obj_stage_moving; with one copy the model is
+// one moving placement).  --shutter T0,T1 (0 <= T0 <= T1 <= 1) replaces the
+// camera's shutter interval, [0, 1] in every scene here.
 //
 // --texture is the earth image as a binary PPM (P6; the reference decodes
 // earthmap.jpeg with stb_image, main.cu:497-510 — convert it once, e.g. with
@@ -76,7 +81,18 @@ int main(int argc, char **argv) {
   std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
-  bool copies_given = false;
+  bool copies_given = false, move_given = false, shutter_given = false;
+  double obj_move[3] = {0, 0, 0}, shutter[2] = {0, 1};
+  // "a,b[,c]": exactly n finite numbers separated by commas
+  auto numbers = [](const char *txt, double *out, int n) {
+    for (int k = 0; k < n; ++k) {
+      char *end = nullptr;
+      out[k] = std::strtod(txt, &end);
+      if (end == txt || !std::isfinite(out[k]) || *end != (k + 1 < n ? ',' : '\0')) return false;
+      txt = end + 1;
+    }
+    return true;
+  };
   unsigned long long seed = 1984;
   for (int a = 1; a < argc; a++) {
     auto need = [&](const char *f) -> const char * {
@@ -90,6 +106,16 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--obj-gen-normals")) obj_gen = true;
     else if (!std::strcmp(argv[a], "--obj-texture")) obj_texture = need("--obj-texture");
     else if (!std::strcmp(argv[a], "--obj-copies")) { obj_copies = std::atoi(need("--obj-copies")); copies_given = true; }
+    else if (!std::strcmp(argv[a], "--obj-move")) {
+      move_given = true;
+      if (!numbers(need("--obj-move"), obj_move, 3)) { std::fprintf(stderr, "--obj-move takes DX,DY,DZ\n"); return 2; }
+    } else if (!std::strcmp(argv[a], "--shutter")) {
+      shutter_given = true;
+      if (!numbers(need("--shutter"), shutter, 2) || !(shutter[0] >= 0 && shutter[0] <= shutter[1] && shutter[1] <= 1)) {
+        std::fprintf(stderr, "--shutter takes T0,T1 with 0 <= T0 <= T1 <= 1\n");
+        return 2;
+      }
+    }
     else if (!std::strcmp(argv[a], "--width")) W = std::atoi(need("--width"));
     else if (!std::strcmp(argv[a], "--height")) H = std::atoi(need("--height"));
     else if (!std::strcmp(argv[a], "--spp")) spp = std::atoi(need("--spp"));
@@ -103,14 +129,17 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
                            "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
                            "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]\n"
-                           "          [--obj-texture FILE.ppm] [--obj-copies N] [--width W] [--height H] ...\n"
+                           "          [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--width W] [--height H] ...\n"
+                           "       either form: [--shutter T0,T1] (the camera's shutter, 0 <= T0 <= T1 <= 1; default 0,1)\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
                            "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
                            "  --obj-smooth: interpolated vn (--obj-gen-normals: generated where missing);\n"
                            "  --obj-texture: a P6 image mapped by vt (lambertian, metal); all three need --obj\n"
                            "  --obj-copies N (1..256, needs --obj): the model as one shared mesh placed N x N times, 3 units\n"
-                           "         apart, each copy turned and nudged by a fixed formula; the camera backs away with N\n",
+                           "         apart, each copy turned and nudged by a fixed formula; the camera backs away with N\n"
+                           "  --obj-move DX,DY,DZ (needs --obj): every placement of the model moves by that vector over the\n"
+                           "         times [0, 1] (motion blur under the default shutter)\n",
                    argv[0], argv[0]);
       return 2;
     }
@@ -127,6 +156,10 @@ int main(int argc, char **argv) {
   }
   if (copies_given && (obj.empty() || obj_copies < 1 || obj_copies > 256)) {
     std::fprintf(stderr, "--obj-copies needs --obj and a count in 1..256\n");
+    return 2;
+  }
+  if (move_given && obj.empty()) {
+    std::fprintf(stderr, "--obj-move needs --obj\n");
     return 2;
   }
   const int obj_kind = obj_mat == "lambertian" ? RT_NW_LAMBERTIAN : obj_mat == "metal" ? RT_NW_METAL : obj_mat == "glass" ? RT_NW_DIELECTRIC : -1;
@@ -155,7 +188,11 @@ int main(int argc, char **argv) {
   if ((rc = rt_nw_scene_create(&s))) return die("rt_nw_scene_create", rc);
   if (!obj.empty()) {
     const uint32_t flags = (obj_smooth ? RT_NW_MESH_SMOOTH : 0) | (obj_gen ? RT_NW_MESH_GEN_NORMALS : 0) | (oimg.empty() ? 0 : RT_NW_MESH_UV);
-    if (obj_copies > 1) {
+    if (move_given) {
+      if ((rc = rt_nw_scene_obj_stage_moving(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh, obj_copies,
+                                             obj_move, double(W) / H, &cam, nullptr)))
+        return die("rt_nw_scene_obj_stage_moving", rc);
+    } else if (obj_copies > 1) {
       if ((rc = rt_nw_scene_obj_stage_copies(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh, obj_copies,
                                              double(W) / H, &cam, nullptr)))
         return die("rt_nw_scene_obj_stage_copies", rc);
@@ -168,6 +205,10 @@ int main(int argc, char **argv) {
   } else if ((rc = rt_nw_scene_preset(s, which, img.empty() ? nullptr : img.data(), iw, ih, double(W) / H,
                                       rtl ? RT_NW_ARGS_RTL : 0, &cam))) {
     return die("rt_nw_scene_preset", rc);
+  }
+  if (shutter_given) {
+    cam.time0 = shutter[0];
+    cam.time1 = shutter[1];
   }
   rt_nw_ctx *ctx = nullptr;
   if ((rc = rt_nw_ctx_create(0, &ctx))) return die("rt_nw_ctx_create", rc);

@@ -66,6 +66,11 @@ struct DeviceScene {
   std::vector<int32_t> pool_j;       // pool slot -> index j in its mesh's flatten order (insertion index first(p) + j)
   std::vector<int32_t> pool_attr;    // attribute record of a pool slot or -1; empty when obj_attr is
   std::vector<Node> bnodes;          // the bottom-level BVHs, one after the other
+  // Moving placements (rt_nw_move, DESIGN.md §9 "Moving placements"): how many
+  // kInstance records carry a motion (aux = 1; rtmi_nw_types.h kInstance).  Each
+  // has an Inst of its own at the end of inst, holding o0; its top-level box
+  // is swept over the render times [0, 1].
+  int32_t n_moving = 0;
 };
 
 // Flatten the world and build the BVH (RT_OK or RT_E*).

@@ -184,6 +184,31 @@ template <class O> __device__ __forceinline__ V moving_center(const O &ob, float
   return mk(__builtin_fmaf(f, ob.g1[0] - ob.g0[0], ob.g0[0]), __builtin_fmaf(f, ob.g1[1] - ob.g0[1], ob.g0[1]),
             __builtin_fmaf(f, ob.g1[2] - ob.g0[2], ob.g0[2]));
 }
+// A moving placement (rt_nw_move; TRI = 4) follows the same rule for its
+// translation.  The specification of off(T), the offset at ray time T:
+//  1. o0, o1: the placement's composed translations with the node at offset0
+//     and at offset1, each composed in double through compose_translate /
+//     compose_rotate exactly as a static rt_nw_translate would be, then
+//     rounded to float (o0 sits in the placement's Inst, o1 in its record);
+//  2. f = (time0 == 0 && time1 == 1) ? T : (T - time0) / (time1 - time0), in
+//     float: moving_center's rule above;
+//  3. off(T)[a] = o0[a] + f * (o1[a] - o0[a]) in float: a subtract, a multiply
+//     and an add, each rounded, never fused (unlike the sphere's centre, which
+//     restates the reference's contracted expression), so numpy float32
+//     reproduces it.
+// rtmi_nw_types.h motion_offset is the one place this is written, for the
+// host's flat view (rt_nw_scene_flat_at) and the kernels alike.
+// The Inst of top-level record `ob` (a placement) for a ray at `time`
+template <bool MOVE> __device__ __forceinline__ Inst placement_inst(const View &sc, const DevObj &ob, float time) {
+  Inst in = sc.inst[ob.inst];
+  if constexpr (MOVE) {
+    if (ob.ka >> 8) {  // moving: g1[1..3] = o1, mat = time0's bits, t1 = time1
+      const float o0[3] = {in.off[0], in.off[1], in.off[2]}, o1[3] = {ob.g1[1], ob.g1[2], ob.g1[3]};
+      motion_offset(o0, o1, __int_as_float(ob.mat), ob.t1, time, in.off);
+    }
+  }
+  return in;
+}
 // moving_sphere::hit moving_sphere.h:48-77: disc >= 0, roots in [t_min, t_max]
 __device__ __forceinline__ bool hit_moving(V o, V d, V c, float r, float tmin, float tmax, float &t) {
   const V oc = sub3(o, c);
@@ -900,9 +925,11 @@ __device__ __forceinline__ AttrView attr_view_of(const View &sc) {
 }
 
 // slot: the object's leaf-order slot (read only by TRI = 2, with av)
-template <bool S = false, int TRI = 0>
+// IN: the object's Inst is *in_given (a moving placement's, formed by the caller) instead of sc.inst[ob.inst]
+template <bool S = false, int TRI = 0, bool IN = false>
 __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, V dw, float time, float t, int face,
-                                        AttrView av = AttrView{nullptr, nullptr}, int32_t slot = 0) {
+                                        AttrView av = AttrView{nullptr, nullptr}, int32_t slot = 0,
+                                        const Inst *in_given = nullptr) {
   Rec r;
   r.mat = ob.mat;
   r.u = 0.0f;
@@ -918,7 +945,8 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
   V o = ow, d = dw;
   Inst in{1.f, 0.f, {0.f, 0.f, 0.f}, 0, {0, 0}};
   if (ob.inst >= 0) {
-    in = sc.inst[ob.inst];
+    if constexpr (IN) in = *in_given;
+    else in = sc.inst[ob.inst];
     to_local(in, o, d);
   }
   V p = at3(o, d, t), n;
@@ -1042,13 +1070,28 @@ __device__ __forceinline__ int32_t inst_winner_id(const View &sc, int32_t k, int
 }
 // ... and its hit record: the pool triangle under the placement's Inst is the
 // record of the flattened copy (make_rec, attribute path included)
+// MOVE (TRI = 4): a placement flagged moving takes its Inst at the ray's time
+// (placement_inst); a static one the TRI = 3 arithmetic, value for value
+template <bool MOVE = false>
 __device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t sub, V ow, V dw, float time, float t,
                                              int face) {
   const PoolView pv = pool_view_of(sc);
   const int32_t slot = sub >= 0 ? sc.nobj + sub : k;
   DevObj ob = sc.obj[slot];
-  if (sub >= 0) ob.inst = sc.obj[k].inst;
-  return make_rec<false, 2>(sc, ob, ow, dw, time, t, face, pv.av, slot);
+  if constexpr (MOVE) {  // (one make_rec for both cases: a second inlined copy is 8 KB of code)
+    Inst in{1.f, 0.f, {0.f, 0.f, 0.f}, 0, {0, 0}};
+    if (sub >= 0) {
+      const DevObj top = sc.obj[k];
+      ob.inst = top.inst;
+      if (top.inst >= 0) in = placement_inst<true>(sc, top, time);
+    } else if (ob.inst >= 0) {
+      in = sc.inst[ob.inst];
+    }
+    return make_rec<false, 2, true>(sc, ob, ow, dw, time, t, face, pv.av, slot, &in);
+  } else {
+    if (sub >= 0) ob.inst = sc.obj[k].inst;
+    return make_rec<false, 2>(sc, ob, ow, dw, time, t, face, pv.av, slot);
+  }
 }
 
 // hit_world_nw over a scene with placements.  One loop walks both levels: at
@@ -1059,7 +1102,9 @@ __device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t 
 // the top level behind the placement's leaf with the world ray's inverses.
 // Returns the winner's top-level slot (a placement's: best_sub is its pool
 // slot, else -1) or nobj + m for medium m; -1 none.
-template <bool LDS_NODES, bool LDS_OBJS>
+// MOVE (TRI = 4): on entering a placement flagged moving, the Inst of to_local
+// has off replaced by off(time) (placement_inst).
+template <bool LDS_NODES, bool LDS_OBJS, bool MOVE = false>
 __device__ __forceinline__ int32_t hit_world_nw_inst(const View &sc, V o, V d, float time, uint64_t seg_key, float &best_t,
                                                      int &best_face, int32_t &best_sub, NwCount *cnt) {
   const float4 *nlo = LDS_NODES ? nw_nodes_lds : sc.nlo;
@@ -1166,7 +1211,11 @@ __device__ __forceinline__ int32_t hit_world_nw_inst(const View &sc, V o, V d, f
         node = __float_as_int(ob.g0[0]);
         end = __float_as_int(ob.g0[1]);
         pfirst = __float_as_int(ob.g0[3]);
-        if (ob.inst >= 0) to_local(sc.inst[ob.inst], co, cd);
+        if constexpr (MOVE) {
+          if (ob.inst >= 0) to_local(placement_inst<true>(sc, ob, time), co, cd);
+        } else {
+          if (ob.inst >= 0) to_local(sc.inst[ob.inst], co, cd);
+        }
         // tri_ray of the local direction; without an Inst (or a rotation) it is
         // the world ray's trw / invw selection of hit_object, value for value
         axes = tri_axes(cd);

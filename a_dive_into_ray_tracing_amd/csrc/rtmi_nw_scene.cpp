@@ -23,7 +23,7 @@ using namespace rtmi::nw;
 
 namespace {
 
-enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4, kShared = 5 };
+enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4, kShared = 5, kMove = 6 };
 
 struct SNode {
   int type = kPrim;
@@ -31,8 +31,10 @@ struct SNode {
   int32_t attr = -1;           // kPrim, a triangle: its attribute record (rt_nw_scene::attr) or -1
   double g[12] = {0};          // kPrim geometry, double (layout of Obj g0..g2)
   std::vector<int32_t> kids;   // kGroup
-  int32_t child = -1;          // kTranslate / kRotate / kMediumNode / kShared
-  double off[3] = {0, 0, 0};   // kTranslate
+  int32_t child = -1;          // kTranslate / kRotate / kMediumNode / kShared / kMove
+  double off[3] = {0, 0, 0};   // kTranslate; kMove: offset0
+  double off1[3] = {0, 0, 0};  // kMove: offset1
+  double time0 = 0, time1 = 1; // kMove: the times of offset0 and offset1
   double angle = 0;            // kRotate (degrees)
   double density = 0;          // kMediumNode
   int32_t phase_mat = -1;      // kMediumNode: its isotropic material
@@ -45,6 +47,11 @@ struct Xf {
   double theta = 0;  // degrees
   double t[3] = {0, 0, 0};
   bool rot = false, trans = false;
+  // under a rt_nw_move node: t is the translation with the node at offset0, t1
+  // with it at offset1, each composed as a static translate's would be
+  bool moving = false;
+  double t1[3] = {0, 0, 0};
+  double time0 = 0, time1 = 1;
 };
 
 struct Bounds {
@@ -108,6 +115,8 @@ struct rt_nw_scene {
   float background[3] = {0.f, 0.f, 0.f};
   // flattened view (rt_nw_scene_flat), insertion order
   bool flat_valid = false;
+  float flat_time = 0.f;  // the time the moving placements are expanded at (rt_nw_scene_flat_at)
+  int32_t n_moves = 0;    // rt_nw_move nodes made: without one the flat view does not depend on the time
   std::vector<Obj> flat_obj;
   std::vector<int32_t> flat_src;  // the SNode a flattened object came from (twin detection)
   std::vector<int32_t> flat_attr; // its attribute record or -1 (rt_nw_scene_flat_attr)
@@ -151,8 +160,30 @@ Xf compose_translate(const Xf &x, const double off[3]) {
   r.t[0] = x.t[0] + (c * off[0] + sn * off[2]);
   r.t[1] = x.t[1] + off[1];
   r.t[2] = x.t[2] + (-sn * off[0] + c * off[2]);
+  if (x.moving) {
+    r.t1[0] = x.t1[0] + (c * off[0] + sn * off[2]);
+    r.t1[1] = x.t1[1] + off[1];
+    r.t1[2] = x.t1[2] + (-sn * off[0] + c * off[2]);
+  }
   r.trans = true;
   return r;
+}
+// rt_nw_move under x: two translations, composed side by side from here on
+Xf compose_move(const Xf &x, const SNode &n) {
+  Xf r = compose_translate(x, n.off);
+  const Xf b = compose_translate(x, n.off1);
+  for (int a = 0; a < 3; ++a) r.t1[a] = b.t[a];
+  r.moving = true;
+  r.time0 = n.time0;
+  r.time1 = n.time1;
+  return r;
+}
+// o0, o1 of a moving placement: the two composed translations as floats
+void motion_ends(const Xf &x, float o0[3], float o1[3]) {
+  for (int a = 0; a < 3; ++a) {
+    o0[a] = float(x.t[a]);
+    o1[a] = float(x.t1[a]);
+  }
 }
 Xf compose_rotate(const Xf &x, double angle) {
   Xf r = x;
@@ -237,6 +268,7 @@ struct Flattener {
   rt_nw_scene *s;
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int32_t>, int32_t> inst_ids;
   int err = RT_OK;
+  float time = 0.f;  // moving placements are expanded at off(time) (rtmi_nw_types.h motion_offset)
 
   int32_t inst_of(const Xf &x) {
     if (!x.rot && !x.trans) return -1;
@@ -245,6 +277,11 @@ struct Flattener {
     in.c = x.rot ? float(std::cos(th)) : 1.f;
     in.s = x.rot ? float(std::sin(th)) : 0.f;
     for (int a = 0; a < 3; ++a) in.off[a] = x.trans ? float(x.t[a]) : 0.f;
+    if (x.moving) {
+      float o0[3], o1[3];
+      motion_ends(x, o0, o1);
+      motion_offset(o0, o1, float(x.time0), float(x.time1), time, in.off);
+    }
     in.flags = (x.rot ? 1 : 0) | (x.trans ? 2 : 0);
     uint32_t b[5];
     std::memcpy(&b[0], &in.c, 4);
@@ -307,6 +344,7 @@ struct Flattener {
         return;
       case kTranslate: emit(n.child, compose_translate(x, n.off), depth + 1); return;
       case kRotate: emit(n.child, compose_rotate(x, n.angle), depth + 1); return;
+      case kMove: emit(n.child, compose_move(x, n), depth + 1); return;
       case kShared: {  // the flat view is the expansion; the placement is remembered for the device scene
         const int32_t first = int32_t(s->flat_obj.size());
         emit(n.child, x, depth + 1);
@@ -342,15 +380,19 @@ struct Flattener {
   }
 };
 
-int flatten(rt_nw_scene *s) {
-  if (s->flat_valid) return RT_OK;
+// time: the instant moving placements are expanded at; null: whichever view is
+// there (time 0 when there is none)
+int flatten(rt_nw_scene *s, const float *time = nullptr) {
+  if (s->flat_valid && (!time || s->n_moves == 0 || std::memcmp(time, &s->flat_time, sizeof(float)) == 0)) return RT_OK;
+  s->flat_valid = false;
+  s->flat_time = time ? *time : 0.f;
   s->flat_obj.clear();
   s->flat_src.clear();
   s->flat_attr.clear();
   s->flat_bounds.clear();
   s->flat_inst.clear();
   s->flat_place.clear();
-  Flattener f{s, {}, RT_OK};
+  Flattener f{s, {}, RT_OK, s->flat_time};
   for (int32_t id : s->world) f.emit(id, Xf{}, 0);
   if (f.err) return f.err;
   // twins: an object that is also a medium's boundary (the same primitive
@@ -636,7 +678,33 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       if (out.mesh[size_t(it->second)].n_tris != p.count) return set_error(RT_EINVAL, "rt_nw: placements of one mesh differ");
     }
     with_places = s->flat_bounds;
-    for (int pi = 0; pi < n_place; ++pi) with_places.push_back(world_bounds(mb[size_t(out.place_mesh[size_t(pi)])].box, places[size_t(pi)].x));
+    for (int pi = 0; pi < n_place; ++pi) {
+      const Bounds &lb = mb[size_t(out.place_mesh[size_t(pi)])].box;
+      const Xf &x = places[size_t(pi)].x;
+      if (!x.moving) {
+        with_places.push_back(world_bounds(lb, x));
+        continue;
+      }
+      // a moving placement: the union of its boxes at render times 0 and 1 (the
+      // offset is linear in time and camera shutters lie in [0, 1]: the moving
+      // sphere's argument in local_bounds; DESIGN.md §9 "Moving placements")
+      Bounds u;
+      for (int a = 0; a < 3; ++a) {
+        u.lo[a] = INFINITY;
+        u.hi[a] = -INFINITY;
+      }
+      for (double tm : {0.0, 1.0}) {
+        const double f = (tm - x.time0) / (x.time1 - x.time0);
+        Xf at = x;
+        for (int a = 0; a < 3; ++a) at.t[a] = x.t[a] + f * (x.t1[a] - x.t[a]);
+        const Bounds b = world_bounds(lb, at);
+        for (int a = 0; a < 3; ++a) {
+          u.lo[a] = std::min(u.lo[a], b.lo[a]);
+          u.hi[a] = std::max(u.hi[a], b.hi[a]);
+        }
+      }
+      with_places.push_back(u);
+    }
   }
   const std::vector<Bounds> &bounds = n_place > 0 ? with_places : s->flat_bounds;
   const int n_ext = n_all + n_place;
@@ -757,6 +825,8 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
         out.pool_attr.push_back(s->flat_attr[size_t(mb[mi].first + out.pool_j[size_t(out.mesh[mi].pool0) + q])]);
   }
   out.place_slot.assign(size_t(n_place), -1);
+  out.inst = s->flat_inst;
+  out.n_moving = 0;
   for (int k = 0; k < n; ++k) {
     if (bvh.order[k] >= n_all) {  // a placement's record (rtmi_nw_types.h kInstance)
       const int pi = bvh.order[k] - n_all;
@@ -770,6 +840,21 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       o.mat = 0;
       o.inst = s->flat_obj[size_t(p.first)].inst;  // every object of the expansion carries the same one
       o.aux = 0;
+      if (p.x.moving) {
+        // the flat view's Inst is the placement at one instant; the device takes
+        // an Inst of its own with o0 and the motion in the record's free words
+        // (rtmi_nw_types.h kInstance), and forms off(time) per ray
+        Inst in = s->flat_inst[size_t(o.inst)];
+        float o1[3];
+        motion_ends(p.x, in.off, o1);
+        out.inst.push_back(in);
+        o.inst = int32_t(out.inst.size()) - 1;
+        for (int a = 0; a < 3; ++a) o.g1[1 + a] = o1[a];
+        o.g2[0] = float(p.x.time1);
+        o.g2[1] = float(p.x.time0);
+        o.aux = 1;
+        ++out.n_moving;
+      }
       out.obj[k] = o;
       out.obj_id[k] = p.first;
       if (any_attr) out.obj_attr[k] = -1;
@@ -790,7 +875,6 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   } else {
     build_obj_grid(s->flat_bounds, margin, bvh.order, out);
   }
-  out.inst = s->flat_inst;
   out.mat = s->mat;
   out.tex = s->tex;
   out.perlin_vec = s->perlin_vec;
@@ -1346,8 +1430,10 @@ RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, in
 // the mesh's lambertian or metal material.
 namespace {
 int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb, int32_t w, int32_t h,
-              double aspect, rt_nw_camera *cam, int32_t *n_tris, int32_t copies = 1) {
+              double aspect, rt_nw_camera *cam, int32_t *n_tris, int32_t copies = 1, const double *move = nullptr) {
   if (!s || !path || !cam || !(aspect > 0) || !mesh_flags_ok(flags)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
+  if (move && !(std::isfinite(float(move[0])) && std::isfinite(float(move[1])) && std::isfinite(float(move[2]))))
+    return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: move vector not finite");
   if (copies < 1 || copies > 256) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: copies must be in 1..256");
   if (mat_kind != RT_NW_LAMBERTIAN && mat_kind != RT_NW_METAL && mat_kind != RT_NW_DIELECTRIC)
     return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: material must be lambertian, metal or dielectric");
@@ -1383,7 +1469,10 @@ int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags
   const int light = chk(rt_nw_rect(s, RT_NW_XZ, -1.5, 1.5, -1.5, 1.5, 5.0, chk(rt_nw_mat_diffuse_light(s, chk(rt_nw_tex_solid(s, 6, 6, 6))))));
   if (rc) return rc;
   chk(rt_nw_world_add(s, ground));
-  if (copies == 1) {
+  const double still[3] = {0, 0, 0};
+  if (copies == 1 && move) {  // one moving placement of the model as a shared mesh
+    chk(rt_nw_world_add(s, chk(rt_nw_move(s, chk(rt_nw_shared(s, mesh)), still, move, 0.0, 1.0))));
+  } else if (copies == 1) {
     chk(rt_nw_world_add(s, mesh));
   } else {
     // copies x copies placements of the one shared mesh, 3 units apart and
@@ -1396,7 +1485,8 @@ int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags
         const int q = i * copies + k;
         const double off[3] = {3.0 * (i - 0.5 * (copies - 1)) + 0.4 * std::sin(1.7 * q), 0.0,
                                3.0 * (k - 0.5 * (copies - 1)) + 0.4 * std::cos(2.3 * q)};
-        chk(rt_nw_world_add(s, chk(rt_nw_translate(s, chk(rt_nw_rotate_y(s, shared, 37.0 * q)), off))));
+        const int placed = chk(rt_nw_translate(s, chk(rt_nw_rotate_y(s, shared, 37.0 * q)), off));
+        chk(rt_nw_world_add(s, move ? chk(rt_nw_move(s, placed, still, move, 0.0, 1.0)) : placed));
         if (rc) return rc;
       }
   }
@@ -1428,12 +1518,20 @@ RTMI_EXPORT int rt_nw_scene_obj_stage_copies(rt_nw_scene *s, const char *path, i
   return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris, copies);
 }
 
+RTMI_EXPORT int rt_nw_scene_obj_stage_moving(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags,
+                                             const uint8_t *rgb, int32_t w, int32_t h, int32_t copies, const double move[3],
+                                             double aspect, rt_nw_camera *cam, int32_t *n_tris) {
+  if (!move) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage_moving: null move vector");
+  return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris, copies, move);
+}
+
 RTMI_EXPORT int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex) {
   if (!s || !valid_node(s, boundary) || !valid_tex(s, tex) || !(density > 0))
     return set_error(RT_EINVAL, "rt_nw_constant_medium: bad argument");
   {  // a triangle (under any translate / rotate_y chain) bounds no volume
     int32_t b = boundary;
-    while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate)) b = s->nodes[b].child;
+    while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate || s->nodes[b].type == kMove))
+      b = s->nodes[b].child;
     if (valid_node(s, b) && ((s->nodes[b].type == kPrim && s->nodes[b].kind == kTriangle) || s->nodes[b].type == kShared))
       return set_error(RT_EUNSUPPORTED, "rt_nw_constant_medium: a triangle cannot be a medium's boundary");
   }
@@ -1513,6 +1611,44 @@ RTMI_EXPORT int rt_nw_shared(rt_nw_scene *s, int32_t object) {
   return add_node(s, n);
 }
 
+RTMI_EXPORT int rt_nw_move(rt_nw_scene *s, int32_t object, const double offset0[3], const double offset1[3], double time0,
+                           double time1) {
+  if (!s || !offset0 || !offset1 || !valid_node(s, object)) return set_error(RT_EINVAL, "rt_nw_move: bad argument");
+  if (!std::isfinite(float(time0)) || !std::isfinite(float(time1)) || float(time0) == float(time1))
+    return set_error(RT_EINVAL, "rt_nw_move: times must be finite and differ (as floats: the kernels divide by their difference)");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(float(offset0[a])) || !std::isfinite(float(offset1[a])))
+      return set_error(RT_EINVAL, "rt_nw_move: offset not finite");
+  // under it: one shared handle, optionally under translate / rotate_y nodes
+  int32_t b = object;
+  for (int depth = 0; s->nodes[size_t(b)].type == kTranslate || s->nodes[size_t(b)].type == kRotate; ++depth) {
+    if (depth > 64) return set_error(RT_EINVAL, "rt_nw_move: object nesting deeper than 64 (a cycle?)");
+    b = s->nodes[size_t(b)].child;
+  }
+  if (s->nodes[size_t(b)].type == kMove) return set_error(RT_EUNSUPPORTED, "rt_nw_move: a move under a move");
+  if (s->nodes[size_t(b)].type != kShared)
+    return set_error(RT_EUNSUPPORTED, "rt_nw_move: only a placement of a shared mesh (rt_nw_shared) can move");
+  SNode n;
+  n.type = kMove;
+  n.child = object;
+  for (int a = 0; a < 3; ++a) {
+    n.off[a] = offset0[a];
+    n.off1[a] = offset1[a];
+  }
+  n.time0 = time0;
+  n.time1 = time1;
+  ++s->n_moves;
+  return add_node(s, n);
+}
+
+RTMI_EXPORT int rt_nw_scene_motion_stats(rt_nw_scene *s, int32_t out[2]) {
+  if (!s || !out) return set_error(RT_EINVAL, "rt_nw_scene_motion_stats: null");
+  if (int rc = flatten(s)) return rc;
+  out[0] = out[1] = 0;
+  for (const rt_nw_scene::Place &p : s->flat_place) ++out[p.x.moving ? 0 : 1];
+  return RT_OK;
+}
+
 RTMI_EXPORT int rt_nw_scene_instancing_stats(rt_nw_scene *s, int32_t out[6]) {
   return rtmi::nw::scene_instancing_stats(s, out);
 }
@@ -1537,9 +1673,13 @@ RTMI_EXPORT int rt_nw_scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *
   return rtmi::nw::scene_grid_stats(s, dims3, max_cell, n_big, n_refs);
 }
 
-RTMI_EXPORT int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out) {
+RTMI_EXPORT int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out) { return rt_nw_scene_flat_at(s, 0.0, out); }
+
+RTMI_EXPORT int rt_nw_scene_flat_at(rt_nw_scene *s, double time, rt_nw_flat *out) {
   if (!s || !out) return set_error(RT_EINVAL, "null");
-  if (int rc = flatten(s)) return rc;
+  const float tf = float(time);
+  if (!std::isfinite(tf)) return set_error(RT_EINVAL, "rt_nw_scene_flat_at: time not finite");
+  if (int rc = flatten(s, &tf)) return rc;
   out->n_obj = int32_t(s->flat_obj.size());
   out->n_inst = int32_t(s->flat_inst.size());
   out->n_mat = int32_t(s->mat.size());

@@ -24,7 +24,10 @@ enum ObjKind : int32_t {
                       //                     view): g0 as int32 bits = {first bottom-level node, one past its
                       //                     last, first pool slot, first(p): the insertion index of the
                       //                     placement's triangle 0}, g1.x as int32 bits = pool slots of the mesh;
-                      //                     inst = the placement's Inst or -1 (DESIGN.md §9 "Shared meshes")
+                      //                     inst = the placement's Inst or -1 (DESIGN.md §9 "Shared meshes").
+                      //                     A moving placement (rt_nw_move): aux = 1, its Inst holds o0,
+                      //                     g1[1..3] = o1, g2 = {time1, time0} (DevObj: t1 = time1, mat = the bits
+                      //                     of time0; a static placement's are zero)
 };
 
 // material kinds = RT_NW_* (rtmi_nw.h)
@@ -65,6 +68,33 @@ struct Inst {  // 32 B; world = translate(rotate_y(local)) (hittable.h:49-189)
   int32_t flags;   // bit 0 rotation present, bit 1 translation present
   int32_t pad[2];
 };
+// The translation of a moving placement (rt_nw_move) at ray time T — the one
+// place it is written, for the host's flat view (rt_nw_scene_flat_at) and the
+// TRI = 4 kernels alike.  o0, o1: the placement's composed translations with
+// the node at offset0 and at offset1, each rounded to float; f is
+// moving_center's rule (rtmi_nw_path.h).  A subtract, a multiply and an add,
+// each rounded on its own: contraction is switched off here whatever the
+// command line says, so numpy float32 reproduces the value exactly.
+#if defined(__HIPCC__)
+#define RTMI_NW_HD __host__ __device__
+#else
+#define RTMI_NW_HD
+#endif
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+RTMI_NW_HD inline void motion_offset(const float o0[3], const float o1[3], float time0, float time1, float T, float out[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float f = (time0 == 0.0f && time1 == 1.0f) ? T : (T - time0) / (time1 - time0);
+  for (int a = 0; a < 3; ++a) {
+    const float d = o1[a] - o0[a];
+    const float fd = f * d;
+    out[a] = o0[a] + fd;
+  }
+}
+
 struct Mat {  // 16 B
   int32_t kind, tex;
   float fuzz, ir;

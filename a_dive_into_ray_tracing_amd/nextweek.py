@@ -165,9 +165,9 @@ class Scene:
         {"attr": float32 n x 16 (normals 9, uvs 6, flags as int bits),
         "attr_of_obj": int32 per flattened object, -1: none}."""
         n, a, o = C.c_int32(), _fp(), _ip()
-        check(load().rt_nw_scene_flat_attr(self._h, C.byref(n), C.byref(a), C.byref(o)), "rt_nw_scene_flat_attr")
-        fl = RtNwFlat()
+        fl = RtNwFlat()  # (the object count; taken first: a flat view at another time invalidates the pointers)
         check(load().rt_nw_scene_flat(self._h, C.byref(fl)), "rt_nw_scene_flat")
+        check(load().rt_nw_scene_flat_attr(self._h, C.byref(n), C.byref(a), C.byref(o)), "rt_nw_scene_flat_attr")
         attr = np.ctypeslib.as_array(a, shape=(16 * n.value,)).copy() if n.value else np.zeros(0, np.float32)
         of = np.ctypeslib.as_array(o, shape=(fl.n_obj,)).copy() if fl.n_obj else np.zeros(0, np.int32)
         return {"attr": attr.astype(np.float32).reshape(-1, 16), "attr_of_obj": of.astype(np.int32)}
@@ -192,6 +192,18 @@ class Scene:
         the image is that of the copies, bit for bit (rt_nw_shared)."""
         return _id(load().rt_nw_shared(self._h, obj), "rt_nw_shared")
 
+    def move(self, obj, off0, off1, t0=0.0, t1=1.0):
+        """A translate node whose offset is linear in the ray's time: off0 at t0,
+        off1 at t1 (rt_nw_move).  `obj`: one shared handle, optionally under
+        translate / rotate_y nodes."""
+        return _id(load().rt_nw_move(self._h, obj, _v3(off0), _v3(off1), float(t0), float(t1)), "rt_nw_move")
+
+    def motion_stats(self):
+        """(moving placements reached from the world, static placements) (rt_nw_scene_motion_stats)."""
+        v = (C.c_int32 * 2)()
+        check(load().rt_nw_scene_motion_stats(self._h, v), "rt_nw_scene_motion_stats")
+        return v[0], v[1]
+
     def add(self, obj):
         check(load().rt_nw_world_add(self._h, obj), "rt_nw_world_add")
         return self
@@ -199,10 +211,15 @@ class Scene:
     def set_background(self, r, g, b):
         check(load().rt_nw_set_background(self._h, r, g, b), "rt_nw_set_background")
 
-    def flat(self):
-        """The flattened scene (what the GPU renders), as numpy arrays (copies)."""
+    def flat(self, time=None):
+        """The flattened scene (what the GPU renders), as numpy arrays (copies).
+        time: the instant moving placements (Scene.move) are expanded at
+        (rt_nw_scene_flat_at); None: rt_nw_scene_flat, which is time 0."""
         f = RtNwFlat()
-        check(load().rt_nw_scene_flat(self._h, C.byref(f)), "rt_nw_scene_flat")
+        if time is None:
+            check(load().rt_nw_scene_flat(self._h, C.byref(f)), "rt_nw_scene_flat")
+        else:
+            check(load().rt_nw_scene_flat_at(self._h, float(time), C.byref(f)), "rt_nw_scene_flat_at")
 
         def arr(p, n, dt=np.float32):
             return np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy() if n else np.zeros(0, dt)
@@ -268,17 +285,30 @@ def _mesh_flags(smooth, uv, gen_normals):
     return (1 if smooth else 0) | (2 if uv else 0) | (4 if gen_normals else 0)
 
 
-def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None, copies=1):
+def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None, copies=1, move=None):
     """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera:
     (scene, camera, triangle count).  smooth / gen_normals as Scene.load_obj;
     texture (h x w x 3 uint8): the mesh's texture, mapped by the file's vt
     (rt_nw_scene_obj_stage_attr; none of them: rt_nw_scene_obj_stage).
     copies = N > 1 (`--obj-copies N`): the model as one shared mesh placed in an
-    N x N field (rt_nw_scene_obj_stage_copies)."""
+    N x N field (rt_nw_scene_obj_stage_copies).  move (`--obj-move DX,DY,DZ`):
+    every placement moves by that vector over [0, 1]
+    (rt_nw_scene_obj_stage_moving)."""
     kind = {"lambertian": 0, "metal": 1, "glass": 2, "dielectric": 2}[mat]
     s = Scene()
     cam = RtNwCamera()
     n = C.c_int32()
+    if move is not None:
+        if texture is not None:
+            a = np.ascontiguousarray(texture, np.uint8)
+            ptr, ih, iw = a.ctypes.data_as(_u8), a.shape[0], a.shape[1]
+        else:
+            ptr, ih, iw = None, 0, 0
+        check(load().rt_nw_scene_obj_stage_moving(s._h, str(path).encode(), kind,
+                                                  _mesh_flags(smooth, texture is not None, gen_normals), ptr, iw, ih,
+                                                  int(copies), _v3(move), float(aspect), C.byref(cam), C.byref(n)),
+              "rt_nw_scene_obj_stage_moving")
+        return s, cam, n.value
     if copies != 1:
         if texture is not None:
             a = np.ascontiguousarray(texture, np.uint8)
@@ -362,14 +392,21 @@ class NwRenderer:
         check(load().rt_nw_render_rows(self._h, C.byref(cam), W, H, spp, max_depth, seed, row0, row_step, nrows,
                                        C.c_void_p(dev_ptr), C.c_void_p(stream)), "rt_nw_render_rows")
 
-    def debug_trace(self, cam, W, H, i, j, s, max_depth=50, seed=1984, cap=64):
-        """The segments of one camera sample: rows (o.xyz, d.xyz, t, n.xyz) and (winner index, box face)."""
+    def debug_trace(self, cam, W, H, i, j, s, max_depth=50, seed=1984, cap=64, with_time=False):
+        """The segments of one camera sample: rows (o.xyz, d.xyz, t, n.xyz) and (winner index, box face);
+        with_time: and the sample's ray time (rt_nw_debug_trace_t)."""
         rec = np.zeros(12 * cap, np.float32)
         n = C.c_int32()
-        check(load().rt_nw_debug_trace(self._h, C.byref(cam), W, H, max_depth, seed, i, j, s, rec.ctypes.data_as(_fp), cap,
-                                       C.byref(n)), "rt_nw_debug_trace")
+        tm = C.c_float()
+        if with_time:
+            check(load().rt_nw_debug_trace_t(self._h, C.byref(cam), W, H, max_depth, seed, i, j, s, rec.ctypes.data_as(_fp),
+                                             cap, C.byref(n), C.byref(tm)), "rt_nw_debug_trace_t")
+        else:
+            check(load().rt_nw_debug_trace(self._h, C.byref(cam), W, H, max_depth, seed, i, j, s, rec.ctypes.data_as(_fp),
+                                           cap, C.byref(n)), "rt_nw_debug_trace")
         out = rec[: 12 * n.value].reshape(-1, 12).copy()
-        return out[:, [0, 1, 2, 3, 4, 5, 6, 8, 9, 10]], out[:, [7, 11]].view(np.int32)
+        segs = out[:, [0, 1, 2, 3, 4, 5, 6, 8, 9, 10]], out[:, [7, 11]].view(np.int32)
+        return (*segs, np.float32(tm.value)) if with_time else segs
 
     def debug_hits(self, rays, keys=None):
         """Closest hit of each ray (rows o.xyz, d.xyz, time) through the walk
@@ -404,6 +441,12 @@ class NwRenderer:
     def last_segments(self):
         v = C.c_uint64()
         check(load().rt_nw_ctx_last_segments(self._h, C.byref(v)), "rt_nw_ctx_last_segments")
+        return v.value
+
+    def scene_tri(self):
+        """Diagnostic: the kernel family of the resident scene, 0..4 (rt_nw_ctx_scene_tri)."""
+        v = C.c_int32()
+        check(load().rt_nw_ctx_scene_tri(self._h, C.byref(v)), "rt_nw_ctx_scene_tri")
         return v.value
 
     def last_kernel(self):

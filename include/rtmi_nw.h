@@ -159,6 +159,12 @@ int rt_nw_scene_obj_stage_copies(rt_nw_scene *s, const char *path, int32_t mat_k
  * sphere, moving sphere or box object, optionally under translate/rotate_y
  * (a rectangle, a triangle, a shared handle or a set of objects:
  * RT_EUNSUPPORTED). */
+/* rt_nw_scene_obj_stage_copies with every placement under rt_nw_move from (0,
+ * 0, 0) to `move` over [0, 1] (`rtmi_nw_render --obj-move`); copies == 1: the
+ * model as one moving placement of a shared mesh. */
+int rt_nw_scene_obj_stage_moving(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
+                                 int32_t w, int32_t h, int32_t copies, const double move[3], double aspect,
+                                 rt_nw_camera *cam, int32_t *n_tris);
 int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex);
 /* Scattering-distance samples of a medium per ray segment (1..8, default 1):
  * each draws -log(u)/density anew and the last one that lands inside the
@@ -189,6 +195,24 @@ int rt_nw_rotate_y(rt_nw_scene *s, int32_t object, double angle_deg);       /* h
  * a translate or rotate node, a medium, another shared handle — is
  * RT_EUNSUPPORTED; no triangle under it: RT_EINVAL. */
 int rt_nw_shared(rt_nw_scene *s, int32_t object);
+/* A translate node whose offset is linear in the ray's time, like
+ * moving_sphere's centre: offset0 at time0, offset1 at time1, extrapolated
+ * outside that interval (camera shutters lie in [0, 1]).  A new handle, used
+ * like rt_nw_translate's.  Only a placement of a shared mesh can move: the
+ * subtree of `object` must be one rt_nw_shared handle, optionally under
+ * rt_nw_translate / rt_nw_rotate_y nodes — a primitive, a group, a medium, a
+ * flattened mesh, or another rt_nw_move above or below: RT_EUNSUPPORTED; as a
+ * medium's boundary: RT_EUNSUPPORTED.  time0 == time1, a time not finite or an
+ * offset not finite as a float: RT_EINVAL.  offset0 == offset1 is legal.
+ * The translation at ray time T (DESIGN.md §9 "Moving placements"): o0 and o1
+ * are the placement's composed translations with the node at offset0 and at
+ * offset1, each composed in double as a static rt_nw_translate's and rounded to
+ * float; f = T when (time0, time1) == (0, 1), else (T - time0) / (time1 -
+ * time0); off(T) = o0 + f * (o1 - o0), every operation a float operation
+ * rounded on its own.  The image at the instant T (shutter [T, T]) is that of
+ * the static scene rt_nw_scene_flat_at(T) describes, bit for bit. */
+int rt_nw_move(rt_nw_scene *s, int32_t object, const double offset0[3], const double offset1[3], double time0,
+               double time1);
 int rt_nw_world_add(rt_nw_scene *s, int32_t object);
 int rt_nw_set_background(rt_nw_scene *s, double r, double g, double b);
 
@@ -230,7 +254,14 @@ typedef struct rt_nw_flat {
   int64_t image_bytes;
   float background[3];
 } rt_nw_flat;
-int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out);
+int rt_nw_scene_flat(rt_nw_scene *s, rt_nw_flat *out); /* = rt_nw_scene_flat_at(s, 0.0, out) */
+/* The flat view with every moving placement (rt_nw_move) expanded at the
+ * instant float(time): its `inst` rows hold off(float(time)) with the
+ * translation flag set; everything else as rt_nw_scene_flat, and the same
+ * bytes at any time for a scene without a move node.  Pointers stay valid
+ * until the scene is modified or a flat view at another time is taken;
+ * rt_nw_scene_flat_attr follows the last flat view taken. */
+int rt_nw_scene_flat_at(rt_nw_scene *s, double time, rt_nw_flat *out);
 /* The triangle attribute records beside rt_nw_scene_flat (same lifetime):
  *   attr        : n_attr * 16 floats: the unit normals of v0, v1, v2 (9), their
  *                 uvs (6), flags as int32 bits (bit 0 normals, bit 1 uvs; the
@@ -249,6 +280,9 @@ int rt_nw_scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *max_cell, in
  * per placement), top-level BVH nodes}.  Without a placement the first four
  * are zero. */
 int rt_nw_scene_instancing_stats(rt_nw_scene *s, int32_t out[6]);
+/* Host only: {moving placements (under a rt_nw_move) reached from the world,
+ * static placements}. */
+int rt_nw_scene_motion_stats(rt_nw_scene *s, int32_t out[2]);
 
 /* ---- device ------------------------------------------------------------ */
 int rt_nw_ctx_create(int32_t device, rt_nw_ctx **out);
@@ -291,6 +325,9 @@ int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_
  * xyz and the box face (int32 bits, -1: none).  *n = segments. */
 int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t max_depth,
                       uint64_t seed, int32_t i, int32_t j, int32_t s, float *rec, int32_t cap, int32_t *n);
+/* rt_nw_debug_trace, and *time: the traced sample's ray time. */
+int rt_nw_debug_trace_t(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t max_depth,
+                        uint64_t seed, int32_t i, int32_t j, int32_t s, float *rec, int32_t cap, int32_t *n, float *time);
 /* Validation: the closest hit of n given rays through the walk a render of
  * this context uses (the uniform grid or the BVH: rt_nw_ctx_accel_info) —
  * rays {o.xyz, d.xyz, time, unused} per ray (8 floats), keys the segments'
@@ -312,6 +349,10 @@ int rt_nw_ctx_last_segments(rt_nw_ctx *ctx, uint64_t *segments);
  * media, solid / checker textures: the other kinds' code compiled out),
  * samples per work item}.  Same image for every choice. */
 int rt_nw_ctx_last_kernel(rt_nw_ctx *ctx, int32_t *out4);
+/* Diagnostic: the instantiation family the resident scene renders with — 0 no
+ * triangle, 1 triangles, 2 triangles with attribute records, 3 placements of
+ * shared meshes, 4 placements of which at least one moves. */
+int rt_nw_ctx_scene_tri(rt_nw_ctx *ctx, int32_t *tri);
 /* Diagnostic: what the last render's kernel walked from LDS, {BVH nodes,
  * object records} (1 / 0; the uniform grid stages the objects, no nodes). */
 int rt_nw_ctx_last_staging(rt_nw_ctx *ctx, int32_t out2[2]);
