@@ -148,6 +148,10 @@ SIGNATURES = {
     "rt_nw_scene_obj_stage_moving": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
                                                C.c_int32, C.c_int32, _dp, C.c_double, C.POINTER(RtNwCamera), _ip]),
     "rt_nw_ctx_scene_tri": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_transform": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rt_nw_scene_affine_stats": (C.c_int, [C.c_void_p, _ip]),
+    "rt_nw_scene_obj_stage_tumbled": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8), C.c_int32,
+                                                C.c_int32, C.c_int32, _dp, C.c_double, C.POINTER(RtNwCamera), _ip]),
     "rt_nw_debug_trace_t": (C.c_int, [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 3 + [C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32, _ip, _fp]),
     "rt_nw_debug_records": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _fp, _ip]),
     "rt_nw_constant_medium": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),

@@ -114,6 +114,18 @@ template <bool S> constexpr int persist_waves() { return S ? RTMI_NW_SIMPLE_WAVE
 #ifndef RTMI_NW_MOVE_PER_EU
 #define RTMI_NW_MOVE_PER_EU 4
 #endif
+// Scenes with an affine placement (TRI = 5: TRI = 4's walk with the 3x3 entry
+// for the placements flagged affine).  Like TRI = 4 and unlike TRI = 3:
+// compiled for 8 waves per SIMD (64 VGPRs, 226-228 spilled) the persistent
+// kernels render the fields of profiles/affine/README.md in 88.8 / 130.9 / 169.9
+// / 244.7 ms (every placement an affine map of the rotate_y field's geometry),
+// compiled for 4 (128 VGPRs, no scratch) in 54.1 / 90.7 / 125.7 / 212.0 ms.
+#ifndef RTMI_NW_AFFINE_PER_EU
+#define RTMI_NW_AFFINE_PER_EU 4
+#endif
+constexpr int affine_per_eu(int tri) { return tri == 5 ? RTMI_NW_AFFINE_PER_EU : RTMI_NW_MOVE_PER_EU; }
+// hit_world_nw_inst's / make_rec_inst's mode of a family: 0 static placements, 1 some move, 2 some are affine
+constexpr int inst_mode(int tri) { return tri == 5 ? 2 : tri == 4 ? 1 : 0; }
 constexpr size_t kCuLds = 160 * 1024;
 constexpr size_t kPStaticLds = (sizeof(unsigned long long) * 3 * 64 * kPWaves + 23 * sizeof(float) + 255) / 256 * 256;
 constexpr size_t kPTwoBlockBudget = kCuLds / 2 - kPStaticLds;
@@ -280,7 +292,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
       float t;
       int face;
       int32_t sub = -1;  // the winner's pool slot when it is a placement's triangle (TRI = 3, 4)
-      const int32_t k = TRI >= 3 ? hit_world_nw_inst<LDS_NODES, LDS_OBJS, TRI == 4>(sc, o, d, time, seg_key, t, face, sub, &cnt)
+      const int32_t k = TRI >= 3 ? hit_world_nw_inst<LDS_NODES, LDS_OBJS, inst_mode(TRI)>(sc, o, d, time, seg_key, t, face, sub, &cnt)
                         : GRID   ? hit_world_nw_grid<S, TRI>(sc, o, d, time, seg_key, t, face, &cnt)
                                  : hit_world_nw<LDS_NODES, LDS_OBJS, TRI>(sc, o, d, time, seg_key, t, face, &cnt);
 #if RTMI_NW_PHASES
@@ -290,7 +302,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
         col = mk(T.x * sc.bg[0], T.y * sc.bg[1], T.z * sc.bg[2]);
         done = true;
       } else {
-        const Rec rec = TRI >= 3 && k < sc.nobj ? make_rec_inst<TRI == 4>(sc, k, sub, o, d, time, t, face)
+        const Rec rec = TRI >= 3 && k < sc.nobj ? make_rec_inst<inst_mode(TRI)>(sc, k, sub, o, d, time, t, face)
                         : S || k < sc.nobj      ? make_rec<S, TRI>(sc, sc.obj[k], o, d, time, t, face, attr_view_of(sc), k)
                                                 : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
         const Mat m = sc.mat[rec.mat];
@@ -370,7 +382,8 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
 // TRI (last parameter of both kernels): the scene holds no triangle (0), triangles (1), triangles with
 // attribute records (2; hit_object, make_rec), placements of shared meshes (3; hit_world_nw_inst: BVH
 // shapes only, such a scene has no uniform grid), placements of which some move (4; the same walk with
-// the moving placements' offsets formed at the ray's time)
+// the moving placements' offsets formed at the ray's time), placements of which some are affine (5; the
+// same walk with the 3x3 entry of rtmi_nw_path.h to_local_affine)
 template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, int TRI = 0>
 __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, unsigned long long *__restrict__ accum,
                                                              float *__restrict__ out,
@@ -393,7 +406,7 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
 template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
-__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI == 4 ? RTMI_NW_MOVE_PER_EU : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
+__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI >= 4 ? affine_per_eu(TRI) : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
                                                                   unsigned long long *__restrict__ segments,
@@ -419,7 +432,7 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
 // i, j, sample s): per segment o.xyz, d.xyz, t, winner insertion index (as
 // float bits) — the oracle's or_nw_trace records the same.
 // has_attr: the scene has triangle attribute records (attr_view_of).
-// INST: a scene with placements of shared meshes (the two-level walk); 2: some of them move.
+// INST: a scene with placements of shared meshes (the two-level walk); 2: some of them move; 3: some are affine.
 template <int INST>
 __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i, int j, int s, float *rec, int cap, int *n_out,
                                            int has_attr) {
@@ -441,7 +454,7 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
     float t;
     int face;
     int32_t sub = -1;
-    const int32_t k = INST ? hit_world_nw_inst<false, false, INST == 2>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
+    const int32_t k = INST ? hit_world_nw_inst<false, false, INST - 1>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
                            : hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
@@ -450,7 +463,7 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
     r[11] = __int_as_float(face);
     if (k < 0) break;
     const Rec rc = k >= sc.nobj ? make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time)
-                   : INST       ? make_rec_inst<INST == 2>(sc, k, sub, o, d, time, t, face)
+                   : INST       ? make_rec_inst<INST - 1>(sc, k, sub, o, d, time, t, face)
                                 : make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
@@ -469,6 +482,9 @@ __global__ void trace_inst_kernel(View sc, Args a, int i, int j, int s, float *r
 }
 __global__ void trace_move_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
   trace_body<2>(sc, a, i, j, s, rec, cap, n_out, 0);
+}
+__global__ void trace_affine_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
+  trace_body<3>(sc, a, i, j, s, rec, cap, n_out, 0);
 }
 // The ray time of that camera sample (rt_nw_debug_trace_t): trace_body's draws up to the time
 __global__ void trace_time_kernel(Args a, int i, int j, int s, float *time_out) {
@@ -512,7 +528,7 @@ __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *_
 }
 // ... of a scene with placements of shared meshes: the two-level walk, nodes
 // and records in global memory
-template <bool MOVE>
+template <int MOVE>
 __device__ __forceinline__ void debug_hits_inst_body(const View &sc, const float *__restrict__ rays,
                                                      const unsigned long long *__restrict__ keys, int32_t n,
                                                      int32_t *__restrict__ out_id, float *__restrict__ out_t,
@@ -534,14 +550,21 @@ __global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const flo
                                                               const unsigned long long *__restrict__ keys, int32_t n,
                                                               int32_t *__restrict__ out_id, float *__restrict__ out_t,
                                                               int32_t *__restrict__ out_face) {
-  debug_hits_inst_body<false>(sc, rays, keys, n, out_id, out_t, out_face);
+  debug_hits_inst_body<0>(sc, rays, keys, n, out_id, out_t, out_face);
 }
 // ... some of whose placements move (TRI = 4)
 __global__ __launch_bounds__(256) void debug_hits_move_kernel(View sc, const float *__restrict__ rays,
                                                               const unsigned long long *__restrict__ keys, int32_t n,
                                                               int32_t *__restrict__ out_id, float *__restrict__ out_t,
                                                               int32_t *__restrict__ out_face) {
-  debug_hits_inst_body<true>(sc, rays, keys, n, out_id, out_t, out_face);
+  debug_hits_inst_body<1>(sc, rays, keys, n, out_id, out_t, out_face);
+}
+// ... some of whose placements are affine (TRI = 5)
+__global__ __launch_bounds__(256) void debug_hits_affine_kernel(View sc, const float *__restrict__ rays,
+                                                                const unsigned long long *__restrict__ keys, int32_t n,
+                                                                int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                                int32_t *__restrict__ out_face) {
+  debug_hits_inst_body<2>(sc, rays, keys, n, out_id, out_t, out_face);
 }
 
 // The hit record of n given rays (validation: rt_nw_debug_records): the
@@ -584,7 +607,7 @@ __global__ __launch_bounds__(256) void debug_records_kernel(View sc, const float
   q[6] = rc.u; q[7] = rc.v;
 }
 // ... of a scene with placements of shared meshes (as debug_hits_inst_kernel)
-template <bool MOVE>
+template <int MOVE>
 __device__ __forceinline__ void debug_records_inst_body(const View &sc, const float *__restrict__ rays,
                                                         const unsigned long long *__restrict__ keys, int32_t n,
                                                         int32_t *__restrict__ out_id, float *__restrict__ out_t,
@@ -618,14 +641,21 @@ __global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const 
                                                                  const unsigned long long *__restrict__ keys, int32_t n,
                                                                  int32_t *__restrict__ out_id, float *__restrict__ out_t,
                                                                  float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  debug_records_inst_body<false>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
+  debug_records_inst_body<0>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
 }
 // ... some of whose placements move (TRI = 4)
 __global__ __launch_bounds__(256) void debug_records_move_kernel(View sc, const float *__restrict__ rays,
                                                                  const unsigned long long *__restrict__ keys, int32_t n,
                                                                  int32_t *__restrict__ out_id, float *__restrict__ out_t,
                                                                  float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  debug_records_inst_body<true>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
+  debug_records_inst_body<1>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
+}
+// ... some of whose placements are affine (TRI = 5)
+__global__ __launch_bounds__(256) void debug_records_affine_kernel(View sc, const float *__restrict__ rays,
+                                                                   const unsigned long long *__restrict__ keys, int32_t n,
+                                                                   int32_t *__restrict__ out_id, float *__restrict__ out_t,
+                                                                   float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
+  debug_records_inst_body<2>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
 }
 
 }  // namespace nw
@@ -672,7 +702,8 @@ struct rt_nw_ctx {
   int32_t has_media = 0;
   int32_t has_tri = 0;  // the kernels' TRI: 0 no triangle, 1 triangles, 2 triangles with attribute records,
                         // 3 placements of shared meshes (nobj, nnodes: the top level's), 4 placements of which
-                        // at least one moves (rt_nw_move)
+                        // at least one moves (rt_nw_move), 5 placements of which at least one is affine
+                        // (rt_nw_transform)
   int32_t npool = 0, nbot = 0;  // TRI = 3: pool slots behind obj[nobj], bottom-level nodes behind nodes[2 * nnodes]
   int32_t nattr = 0;    // attribute records behind obj[nobj] (their locator behind obj_id[nobj]); 0: neither exists
   unsigned long long *accum = nullptr;
@@ -828,11 +859,11 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   const int32_t nt = int32_t(ds.tex.size()), nm = int32_t(ds.mat.size()), ni = int32_t(ds.inst.size());
   const int32_t np = int32_t(ds.perlin_perm.size() / (3 * kPerlinN)), nim = int32_t(ds.image.size());
   const bool two_level = !ds.place_mesh.empty();
-  int32_t n_moving = 0;
+  int32_t n_moving = 0, n_affine = 0;
   for (const Obj &o : ds.obj) {
     if (o.mat < 0 || o.mat >= nm || o.inst >= ni || o.kind < kSphere ||
         (o.kind > kBox && o.kind != kTriangle && !(two_level && o.kind == kInstance)) || o.aux < 0 ||
-        o.aux > (o.kind == kInstance ? 1 : int32_t(ds.med.size())))
+        o.aux > (o.kind == kInstance ? 3 : int32_t(ds.med.size())))
       return set_error(RT_EINVAL, "rt_nw: object with bad material/instance/kind");
     if (o.kind != kInstance) continue;
     // a placement's motion words (rtmi_nw_types.h kInstance): all zero, or a
@@ -843,12 +874,35 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
         return set_error(RT_EINVAL, "rt_nw: static placement with motion words");
       continue;
     }
+    if (o.aux & 2) {
+      // an affine placement's words (rtmi_nw_types.h AffInst): its row pair in
+      // range, a finite matrix and offset, the affine flag
+      ++n_affine;
+      if (o.inst < 0 || o.inst + 1 >= ni) return set_error(RT_EINVAL, "rt_nw: affine placement with its rows out of range");
+      AffInst ai;
+      std::memcpy(&ai, &ds.inst[size_t(o.inst)], sizeof ai);
+      bool ok = ai.flags == 4;
+      for (float v : ai.m) ok = ok && std::isfinite(v);
+      for (float v : ai.off) ok = ok && std::isfinite(v);
+      if (!ok) return set_error(RT_EINVAL, "rt_nw: bad affine placement rows");
+      if (o.aux == 2) {
+        if (o.g1[1] != 0.f || o.g1[2] != 0.f || o.g1[3] != 0.f || o.g2[0] != 0.f || o.g2[1] != 0.f)
+          return set_error(RT_EINVAL, "rt_nw: static placement with motion words");
+        continue;
+      }
+      ++n_moving;
+      if (!std::isfinite(o.g1[1]) || !std::isfinite(o.g1[2]) || !std::isfinite(o.g1[3]) || !std::isfinite(o.g2[0]) ||
+          !std::isfinite(o.g2[1]) || o.g2[0] == o.g2[1])
+        return set_error(RT_EINVAL, "rt_nw: bad motion in a placement record");
+      continue;
+    }
     ++n_moving;
     if (o.inst < 0 || !(ds.inst[size_t(o.inst)].flags & 2) || !std::isfinite(o.g1[1]) || !std::isfinite(o.g1[2]) ||
         !std::isfinite(o.g1[3]) || !std::isfinite(o.g2[0]) || !std::isfinite(o.g2[1]) || o.g2[0] == o.g2[1])
       return set_error(RT_EINVAL, "rt_nw: bad motion in a placement record");
   }
   if (n_moving != ds.n_moving) return set_error(RT_EINVAL, "rt_nw: moving placement records do not match the count");
+  if (n_affine != ds.n_affine) return set_error(RT_EINVAL, "rt_nw: affine placement records do not match the count");
   // shared meshes: every link the two-level walk follows (rtmi_nw_path.h hit_world_nw_inst)
   const size_t npool = ds.pool.size(), nbot = ds.bnodes.size();
   if (!two_level && (npool || nbot || !ds.mesh.empty())) return set_error(RT_EINVAL, "rt_nw: shared pool without a placement");
@@ -1035,7 +1089,7 @@ RTMI_EXPORT int rt_nw_ctx_set_scene(rt_nw_ctx *ctx, rt_nw_scene *s) {
   for (const Obj &o : ds.obj) ctx->has_tri |= o.kind == kTriangle ? 1 : 0;
   ctx->nattr = int32_t(nattr);
   if (nattr) ctx->has_tri = 2;
-  if (two_level) ctx->has_tri = ds.n_moving > 0 ? 4 : 3;
+  if (two_level) ctx->has_tri = ds.n_affine > 0 ? 5 : ds.n_moving > 0 ? 4 : 3;
   ctx->npool = int32_t(npool);
   ctx->nbot = int32_t(nbot);
   bool simple = ds.med.empty();
@@ -1152,7 +1206,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   // objects staged beside the nodes only when two blocks still fit a CU (or
   // when one block per CU is all the nodes allow anyway)
   // (the two-level kernels below 8 waves per SIMD run one block per CU whatever they stage)
-  const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8);
+  const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8) ||
+                         (ctx->has_tri == 5 && RTMI_NW_AFFINE_PER_EU < 8);
   const bool p_objs = RTMI_NW_LDS_OBJS && persist &&
                       (node_bytes + obj_bytes <= kPTwoBlockBudget ||
                        ((one_block || node_bytes > kPTwoBlockBudget) && node_bytes + obj_bytes <= kPLdsBudget));
@@ -1188,8 +1243,10 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   using Tri2 = std::integral_constant<int, 2>;
   using Tri3 = std::integral_constant<int, 3>;
   using Tri4 = std::integral_constant<int, 4>;
+  using Tri5 = std::integral_constant<int, 5>;
   if (ctx->has_tri >= 3 && use_grid) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
-  const void *kfn = ctx->has_tri == 4   ? kernel_of(Tri4{})
+  const void *kfn = ctx->has_tri == 5   ? kernel_of(Tri5{})
+                    : ctx->has_tri == 4 ? kernel_of(Tri4{})
                     : ctx->has_tri == 3 ? kernel_of(Tri3{})
                     : ctx->has_tri == 2 ? kernel_of(Tri2{})
                     : ctx->has_tri      ? kernel_of(Tri1{})
@@ -1262,7 +1319,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
       hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
   };
   auto launch = [&](auto chunked) {
-    if (ctx->has_tri == 4) launch_t(chunked, Tri4{});
+    if (ctx->has_tri == 5) launch_t(chunked, Tri5{});
+    else if (ctx->has_tri == 4) launch_t(chunked, Tri4{});
     else if (ctx->has_tri == 3) launch_t(chunked, Tri3{});
     else if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
     else if (ctx->has_tri) launch_t(chunked, Tri1{});
@@ -1320,7 +1378,9 @@ RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   int *d_n = nullptr;
   HIP_TRY(hipMalloc(&d_rec, size_t(cap) * 12 * sizeof(float)));
   HIP_TRY(hipMalloc(&d_n, sizeof(int)));
-  if (ctx->has_tri == 4)
+  if (ctx->has_tri == 5)
+    hipLaunchKernelGGL(trace_affine_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
+  else if (ctx->has_tri == 4)
     hipLaunchKernelGGL(trace_move_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
   else if (ctx->has_tri == 3)
     hipLaunchKernelGGL(trace_inst_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
@@ -1387,7 +1447,9 @@ RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64
   if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
-    if (ctx->has_tri == 4)
+    if (ctx->has_tri == 5)
+      hipLaunchKernelGGL(debug_hits_affine_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
+    else if (ctx->has_tri == 4)
       hipLaunchKernelGGL(debug_hits_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
     else if (ctx->has_tri == 3)
       hipLaunchKernelGGL(debug_hits_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
@@ -1436,7 +1498,10 @@ RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uin
   if (e == hipSuccess) {
     const dim3 grd(unsigned((n + 255) / 256)), blk(256);
     const int has_attr = ctx->nattr > 0 ? 1 : 0;
-    if (ctx->has_tri == 4)
+    if (ctx->has_tri == 5)
+      hipLaunchKernelGGL(debug_records_affine_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
+                         d_mat);
+    else if (ctx->has_tri == 4)
       hipLaunchKernelGGL(debug_records_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
                          d_mat);
     else if (ctx->has_tri == 3)

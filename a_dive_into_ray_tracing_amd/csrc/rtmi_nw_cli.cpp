@@ -8,7 +8,7 @@
 //                  [--spp S] [--depth D] [--seed N] [--texture FILE.ppm]
 //                  [--out FILE|-] [--p6] [--rtl]
 //   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
-//                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--width W] ...
+//                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble] [--width W] ...
 //   either form: [--shutter T0,T1]
 //
 // --obj (exclusive with --scene) renders a Wavefront OBJ mesh
@@ -23,7 +23,9 @@
 // N x N times on the ground (rt_nw_scene_obj_stage_copies; 1: the stage above).
 // --obj-move DX,DY,DZ makes every placement move by that vector over the times
 // [0, 1] (rt_nw_move, rt_nw_scene_obj_stage_moving; with one copy the model is
-// one moving placement).  --shutter T0,T1 (0 <= T0 <= T1 <= 1) replaces the
+// one moving placement).  --obj-tumble makes every copy an affine placement
+// (rt_nw_transform, rt_nw_scene_obj_stage_tumbled): scaled, turned about a skew
+// axis and stood on the ground; it combines with --obj-move.  --shutter T0,T1 (0 <= T0 <= T1 <= 1) replaces the
 // camera's shutter interval, [0, 1] in every scene here.
 //
 // --texture is the earth image as a binary PPM (P6; the reference decodes
@@ -81,7 +83,7 @@ int main(int argc, char **argv) {
   std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
-  bool copies_given = false, move_given = false, shutter_given = false;
+  bool copies_given = false, move_given = false, shutter_given = false, tumble = false;
   double obj_move[3] = {0, 0, 0}, shutter[2] = {0, 1};
   // "a,b[,c]": exactly n finite numbers separated by commas
   auto numbers = [](const char *txt, double *out, int n) {
@@ -116,6 +118,7 @@ int main(int argc, char **argv) {
         return 2;
       }
     }
+    else if (!std::strcmp(argv[a], "--obj-tumble")) tumble = true;
     else if (!std::strcmp(argv[a], "--width")) W = std::atoi(need("--width"));
     else if (!std::strcmp(argv[a], "--height")) H = std::atoi(need("--height"));
     else if (!std::strcmp(argv[a], "--spp")) spp = std::atoi(need("--spp"));
@@ -129,7 +132,8 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
                            "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
                            "       %s --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]\n"
-                           "          [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--width W] [--height H] ...\n"
+                           "          [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble]\n"
+                           "          [--width W] [--height H] ...\n"
                            "       either form: [--shutter T0,T1] (the camera's shutter, 0 <= T0 <= T1 <= 1; default 0,1)\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
@@ -139,7 +143,9 @@ int main(int argc, char **argv) {
                            "  --obj-copies N (1..256, needs --obj): the model as one shared mesh placed N x N times, 3 units\n"
                            "         apart, each copy turned and nudged by a fixed formula; the camera backs away with N\n"
                            "  --obj-move DX,DY,DZ (needs --obj): every placement of the model moves by that vector over the\n"
-                           "         times [0, 1] (motion blur under the default shutter)\n",
+                           "         times [0, 1] (motion blur under the default shutter)\n"
+                           "  --obj-tumble (needs --obj): every copy as an affine placement of the shared mesh, scaled by\n"
+                           "         0.75 + 0.25 sin(2.9 q), turned 37 q degrees about a skew axis and stood on the ground\n",
                    argv[0], argv[0]);
       return 2;
     }
@@ -156,6 +162,10 @@ int main(int argc, char **argv) {
   }
   if (copies_given && (obj.empty() || obj_copies < 1 || obj_copies > 256)) {
     std::fprintf(stderr, "--obj-copies needs --obj and a count in 1..256\n");
+    return 2;
+  }
+  if (tumble && obj.empty()) {
+    std::fprintf(stderr, "--obj-tumble needs --obj\n");
     return 2;
   }
   if (move_given && obj.empty()) {
@@ -188,7 +198,11 @@ int main(int argc, char **argv) {
   if ((rc = rt_nw_scene_create(&s))) return die("rt_nw_scene_create", rc);
   if (!obj.empty()) {
     const uint32_t flags = (obj_smooth ? RT_NW_MESH_SMOOTH : 0) | (obj_gen ? RT_NW_MESH_GEN_NORMALS : 0) | (oimg.empty() ? 0 : RT_NW_MESH_UV);
-    if (move_given) {
+    if (tumble) {
+      if ((rc = rt_nw_scene_obj_stage_tumbled(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh, obj_copies,
+                                              move_given ? obj_move : nullptr, double(W) / H, &cam, nullptr)))
+        return die("rt_nw_scene_obj_stage_tumbled", rc);
+    } else if (move_given) {
       if ((rc = rt_nw_scene_obj_stage_moving(s, obj.c_str(), obj_kind, flags, oimg.empty() ? nullptr : oimg.data(), ow, oh, obj_copies,
                                              obj_move, double(W) / H, &cam, nullptr)))
         return die("rt_nw_scene_obj_stage_moving", rc);

@@ -71,6 +71,10 @@ struct DeviceScene {
   // has an Inst of its own at the end of inst, holding o0; its top-level box
   // is swept over the render times [0, 1].
   int32_t n_moving = 0;
+  // Affine placements (rt_nw_transform, DESIGN.md §9 "Affine placements"): how
+  // many kInstance records carry aux bit 1.  Each has two Inst rows of its own
+  // at the end of inst, read as one AffInst (rtmi_nw_types.h).
+  int32_t n_affine = 0;
 };
 
 // Flatten the world and build the BVH (RT_OK or RT_E*).

@@ -149,6 +149,49 @@ __device__ __forceinline__ void to_local(const Inst &in, V &o, V &d) {
     d = mk(__builtin_fmaf(in.c, d.x, -(in.s * d.z)), d.y, __builtin_fmaf(in.s, d.x, in.c * d.z));
   }
 }
+// An affine placement (rt_nw_transform; TRI = 5).  THE SPECIFICATION
+// (tests/native/nw_affine_ref.cpp restates it).  M = float(A^-1) row-major and
+// off = float(b) are the placement's AffInst; o, d the world ray.
+//  ray into the placement's frame:
+//   q = o - off: three float subtractions, always made
+//   lo_i = fmaf(M[i][0], q.x, fmaf(M[i][1], q.y, M[i][2] * q.z))
+//   ld_i = fmaf(M[i][0], d.x, fmaf(M[i][1], d.y, M[i][2] * d.z))
+//   nothing is normalised: o + t d and lo + t ld are the same point for the
+//   same t, so best_t, the t >= 0.001 rule and the (t, insertion index) winner
+//   rule hold across placements as they are
+//   tri_axes / tri_ray and the slab inverses are taken of (lo, ld), as for any
+//   placement (hit_world_nw_inst)
+//  hit: tri_edges and t = T / det unchanged; the winner is the smallest
+//   (t, first(p) + j)
+//  record:
+//   p = at3(o, d, t), from the world ray (no forward matrix is stored)
+//   n_l: the local normal exactly as make_rec forms it in the local frame — the
+//    geometric one, or the smooth one with the side rule evaluated on ld
+//   w_j = fmaf(M[0][j], n_l.x, fmaf(M[1][j], n_l.y, M[2][j] * n_l.z)): the
+//    inverse transpose, the stored matrix read by columns
+//   n = w * drcp(dsqrt(dot3(w, w)))
+//   u, v from the local frame, as for any placement
+//  a moving affine placement: off is off(time) (motion_offset, as
+//   placement_inst forms it); nothing else depends on the time
+//  the other placements of the scene take the TRI = 3 / 4 arithmetic, value for
+//  value
+__device__ __forceinline__ void to_local_affine(const AffInst &in, V &o, V &d) {
+  const V q = mk(o.x - in.off[0], o.y - in.off[1], o.z - in.off[2]);
+  o = mk(__builtin_fmaf(in.m[0], q.x, __builtin_fmaf(in.m[1], q.y, in.m[2] * q.z)),
+         __builtin_fmaf(in.m[3], q.x, __builtin_fmaf(in.m[4], q.y, in.m[5] * q.z)),
+         __builtin_fmaf(in.m[6], q.x, __builtin_fmaf(in.m[7], q.y, in.m[8] * q.z)));
+  d = mk(__builtin_fmaf(in.m[0], d.x, __builtin_fmaf(in.m[1], d.y, in.m[2] * d.z)),
+         __builtin_fmaf(in.m[3], d.x, __builtin_fmaf(in.m[4], d.y, in.m[5] * d.z)),
+         __builtin_fmaf(in.m[6], d.x, __builtin_fmaf(in.m[7], d.y, in.m[8] * d.z)));
+}
+// a local normal -> world under an affine placement, unit length
+__device__ __forceinline__ V normal_to_world_affine(const AffInst &in, V n) {
+  const V w = mk(__builtin_fmaf(in.m[0], n.x, __builtin_fmaf(in.m[3], n.y, in.m[6] * n.z)),
+                 __builtin_fmaf(in.m[1], n.x, __builtin_fmaf(in.m[4], n.y, in.m[7] * n.z)),
+                 __builtin_fmaf(in.m[2], n.x, __builtin_fmaf(in.m[5], n.y, in.m[8] * n.z)));
+  const float il = drcp(dsqrt(dot3(w, w)));
+  return mk(w.x * il, w.y * il, w.z * il);
+}
 // local point / normal -> world (rotate_y hittable.h:162-170, translate :75)
 __device__ __forceinline__ V rot_to_world(const Inst &in, V v) {
   return mk(__builtin_fmaf(in.c, v.x, in.s * v.z), v.y, __builtin_fmaf(-in.s, v.x, in.c * v.z));
@@ -206,6 +249,25 @@ template <bool MOVE> __device__ __forceinline__ Inst placement_inst(const View &
       const float o0[3] = {in.off[0], in.off[1], in.off[2]}, o1[3] = {ob.g1[1], ob.g1[2], ob.g1[3]};
       motion_offset(o0, o1, __int_as_float(ob.mat), ob.t1, time, in.off);
     }
+  }
+  return in;
+}
+// ... in a scene with affine placements (TRI = 5), where aux is a bit set: bit
+// 0 moving, bit 1 affine.  A classical placement's Inst:
+__device__ __forceinline__ Inst placement_inst_bits(const View &sc, const DevObj &ob, float time) {
+  Inst in = sc.inst[ob.inst];
+  if ((ob.ka >> 8) & 1) {
+    const float o0[3] = {in.off[0], in.off[1], in.off[2]}, o1[3] = {ob.g1[1], ob.g1[2], ob.g1[3]};
+    motion_offset(o0, o1, __int_as_float(ob.mat), ob.t1, time, in.off);
+  }
+  return in;
+}
+// ... and an affine placement's AffInst (two Inst rows), off at the ray's time
+__device__ __forceinline__ AffInst placement_affine(const View &sc, const DevObj &ob, float time) {
+  AffInst in = *reinterpret_cast<const AffInst *>(sc.inst + ob.inst);
+  if ((ob.ka >> 8) & 1) {
+    const float o0[3] = {in.off[0], in.off[1], in.off[2]}, o1[3] = {ob.g1[1], ob.g1[2], ob.g1[3]};
+    motion_offset(o0, o1, __int_as_float(ob.mat), ob.t1, time, in.off);
   }
   return in;
 }
@@ -925,11 +987,13 @@ __device__ __forceinline__ AttrView attr_view_of(const View &sc) {
 }
 
 // slot: the object's leaf-order slot (read only by TRI = 2, with av)
-// IN: the object's Inst is *in_given (a moving placement's, formed by the caller) instead of sc.inst[ob.inst]
-template <bool S = false, int TRI = 0, bool IN = false>
+// IN: the object's Inst is *in_given (a moving placement's, formed by the caller) instead of sc.inst[ob.inst];
+// IN = 2 (TRI = 5): or, when is_aff, the affine placement *aff (the specification beside to_local_affine)
+template <bool S = false, int TRI = 0, int IN = 0>
 __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, V dw, float time, float t, int face,
                                         AttrView av = AttrView{nullptr, nullptr}, int32_t slot = 0,
-                                        const Inst *in_given = nullptr) {
+                                        const Inst *in_given = nullptr, const AffInst *aff = nullptr,
+                                        bool is_aff = false) {
   Rec r;
   r.mat = ob.mat;
   r.u = 0.0f;
@@ -945,9 +1009,18 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
   V o = ow, d = dw;
   Inst in{1.f, 0.f, {0.f, 0.f, 0.f}, 0, {0, 0}};
   if (ob.inst >= 0) {
-    if constexpr (IN) in = *in_given;
-    else in = sc.inst[ob.inst];
-    to_local(in, o, d);
+    if constexpr (IN == 2) {
+      if (is_aff) {
+        to_local_affine(*aff, o, d);
+      } else {
+        in = *in_given;
+        to_local(in, o, d);
+      }
+    } else {
+      if constexpr (IN != 0) in = *in_given;
+      else in = sc.inst[ob.inst];
+      to_local(in, o, d);
+    }
   }
   V p = at3(o, d, t), n;
   const Mat mm = sc.mat[ob.mat];
@@ -1025,6 +1098,12 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
     n = rot_to_world(in, n);
   }
   if (in.flags & 2) p = mk(p.x + in.off[0], p.y + in.off[1], p.z + in.off[2]);
+  if constexpr (IN == 2) {
+    if (ob.inst >= 0 && is_aff) {  // (in is the identity here)
+      p = at3(ow, dw, t);
+      n = normal_to_world_affine(*aff, n);
+    }
+  }
   r.p = p;
   r.n = n;
   return r;
@@ -1072,13 +1151,30 @@ __device__ __forceinline__ int32_t inst_winner_id(const View &sc, int32_t k, int
 // record of the flattened copy (make_rec, attribute path included)
 // MOVE (TRI = 4): a placement flagged moving takes its Inst at the ray's time
 // (placement_inst); a static one the TRI = 3 arithmetic, value for value
-template <bool MOVE = false>
+// MOVE = 2 (TRI = 5): and a placement flagged affine its AffInst (placement_affine)
+template <int MOVE = 0>
 __device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t sub, V ow, V dw, float time, float t,
                                              int face) {
   const PoolView pv = pool_view_of(sc);
   const int32_t slot = sub >= 0 ? sc.nobj + sub : k;
   DevObj ob = sc.obj[slot];
-  if constexpr (MOVE) {  // (one make_rec for both cases: a second inlined copy is 8 KB of code)
+  if constexpr (MOVE == 2) {  // (still one make_rec)
+    Inst in{1.f, 0.f, {0.f, 0.f, 0.f}, 0, {0, 0}};
+    AffInst ai{};
+    bool affine = false;
+    if (sub >= 0) {
+      const DevObj top = sc.obj[k];
+      ob.inst = top.inst;
+      if (top.inst >= 0) {
+        affine = ((top.ka >> 8) & 2) != 0;
+        if (affine) ai = placement_affine(sc, top, time);
+        else in = placement_inst_bits(sc, top, time);
+      }
+    } else if (ob.inst >= 0) {
+      in = sc.inst[ob.inst];
+    }
+    return make_rec<false, 2, 2>(sc, ob, ow, dw, time, t, face, pv.av, slot, &in, &ai, affine);
+  } else if constexpr (MOVE == 1) {  // (one make_rec for both cases: a second inlined copy is 8 KB of code)
     Inst in{1.f, 0.f, {0.f, 0.f, 0.f}, 0, {0, 0}};
     if (sub >= 0) {
       const DevObj top = sc.obj[k];
@@ -1087,7 +1183,7 @@ __device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t 
     } else if (ob.inst >= 0) {
       in = sc.inst[ob.inst];
     }
-    return make_rec<false, 2, true>(sc, ob, ow, dw, time, t, face, pv.av, slot, &in);
+    return make_rec<false, 2, 1>(sc, ob, ow, dw, time, t, face, pv.av, slot, &in);
   } else {
     if (sub >= 0) ob.inst = sc.obj[k].inst;
     return make_rec<false, 2>(sc, ob, ow, dw, time, t, face, pv.av, slot);
@@ -1103,8 +1199,9 @@ __device__ __forceinline__ Rec make_rec_inst(const View &sc, int32_t k, int32_t 
 // Returns the winner's top-level slot (a placement's: best_sub is its pool
 // slot, else -1) or nobj + m for medium m; -1 none.
 // MOVE (TRI = 4): on entering a placement flagged moving, the Inst of to_local
-// has off replaced by off(time) (placement_inst).
-template <bool LDS_NODES, bool LDS_OBJS, bool MOVE = false>
+// has off replaced by off(time) (placement_inst).  MOVE = 2 (TRI = 5): and a
+// placement flagged affine is entered through to_local_affine.
+template <bool LDS_NODES, bool LDS_OBJS, int MOVE = 0>
 __device__ __forceinline__ int32_t hit_world_nw_inst(const View &sc, V o, V d, float time, uint64_t seg_key, float &best_t,
                                                      int &best_face, int32_t &best_sub, NwCount *cnt) {
   const float4 *nlo = LDS_NODES ? nw_nodes_lds : sc.nlo;
@@ -1211,7 +1308,12 @@ __device__ __forceinline__ int32_t hit_world_nw_inst(const View &sc, V o, V d, f
         node = __float_as_int(ob.g0[0]);
         end = __float_as_int(ob.g0[1]);
         pfirst = __float_as_int(ob.g0[3]);
-        if constexpr (MOVE) {
+        if constexpr (MOVE == 2) {
+          if (ob.inst >= 0) {
+            if ((ob.ka >> 8) & 2) to_local_affine(placement_affine(sc, ob, time), co, cd);
+            else to_local(placement_inst_bits(sc, ob, time), co, cd);
+          }
+        } else if constexpr (MOVE == 1) {
           if (ob.inst >= 0) to_local(placement_inst<true>(sc, ob, time), co, cd);
         } else {
           if (ob.inst >= 0) to_local(sc.inst[ob.inst], co, cd);

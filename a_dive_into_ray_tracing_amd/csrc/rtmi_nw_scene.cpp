@@ -23,15 +23,15 @@ using namespace rtmi::nw;
 
 namespace {
 
-enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4, kShared = 5, kMove = 6 };
+enum SType { kPrim = 0, kGroup = 1, kTranslate = 2, kRotate = 3, kMediumNode = 4, kShared = 5, kMove = 6, kTransform = 7 };
 
 struct SNode {
   int type = kPrim;
   int32_t kind = 0, mat = -1;  // kPrim
   int32_t attr = -1;           // kPrim, a triangle: its attribute record (rt_nw_scene::attr) or -1
-  double g[12] = {0};          // kPrim geometry, double (layout of Obj g0..g2)
+  double g[12] = {0};          // kPrim geometry, double (layout of Obj g0..g2); kTransform: the row-major 3x4 map
   std::vector<int32_t> kids;   // kGroup
-  int32_t child = -1;          // kTranslate / kRotate / kMediumNode / kShared / kMove
+  int32_t child = -1;          // kTranslate / kRotate / kMediumNode / kShared / kMove / kTransform
   double off[3] = {0, 0, 0};   // kTranslate; kMove: offset0
   double off1[3] = {0, 0, 0};  // kMove: offset1
   double time0 = 0, time1 = 1; // kMove: the times of offset0 and offset1
@@ -52,6 +52,10 @@ struct Xf {
   bool moving = false;
   double t1[3] = {0, 0, 0};
   double time0 = 0, time1 = 1;
+  // with a rt_nw_transform node in the chain (an affine placement): world =
+  // A * local + t, A row-major; theta, rot and trans are not read any more
+  bool affine = false;
+  double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 };
 
 struct Bounds {
@@ -122,6 +126,13 @@ struct rt_nw_scene {
   std::vector<int32_t> flat_attr; // its attribute record or -1 (rt_nw_scene_flat_attr)
   std::vector<Bounds> flat_bounds;
   std::vector<Inst> flat_inst;
+  // affine placements appear baked in the flat view (rt_nw_transform): when one
+  // of them carries attribute records, rt_nw_scene_flat_attr shows attr_view
+  // (attr, then the baked records) and attr_pub (flat_attr with the baked
+  // triangles pointing at theirs); both empty otherwise.  flat_attr itself
+  // always names the local record: the device scene is built from it.
+  std::vector<TriAttr> flat_attr_view;
+  std::vector<int32_t> flat_attr_pub;
   // every occurrence of a shared handle (rt_nw_shared) reached from the world:
   // its kShared node, composed transform, and the flattened objects it
   // expanded to, [first, first + count)
@@ -154,8 +165,62 @@ int add_mat(rt_nw_scene *s, Mat m) {
   return int(s->mat.size()) - 1;
 }
 
+// 3x3 helpers of the affine placements (row-major, double)
+void mat_vec(const double A[9], const double v[3], double out[3]) {
+  for (int i = 0; i < 3; ++i) out[i] = A[3 * i] * v[0] + A[3 * i + 1] * v[1] + A[3 * i + 2] * v[2];
+}
+void mat_mul(const double A[9], const double B[9], double out[9]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+}
+// rotate_y's local-to-world matrix: (x, z) -> (c x + s z, -s x + c z)
+void ry_matrix(double deg, double R[9]) {
+  const double th = deg * M_PI / 180.0, c = std::cos(th), sn = std::sin(th);
+  const double r[9] = {c, 0, sn, 0, 1, 0, -sn, 0, c};
+  for (int i = 0; i < 9; ++i) R[i] = r[i];
+}
+// The conditioning bound of an affine map (rt_nw_transform, and every
+// placement's composite): ||A||_F * ||A^-1||_F <= kAffineCond.  Every matrix
+// with singular values in [1/16, 16] passes (at most 16 sqrt 3 * 16 sqrt 3 =
+// 768); DESIGN.md §9 "Affine placements" derives the margins from it.
+constexpr double kAffineCond = 1024.0;
+// inv = A^-1 (the adjugate over the determinant); false: an entry not finite,
+// det <= 0 (singular or a mirror) or beyond the bound.  cond, when given,
+// receives ||A||_F * ||A^-1||_F.
+bool affine_inverse(const double A[9], double inv[9], double *cond = nullptr) {
+  double fa = 0;
+  for (int i = 0; i < 9; ++i) {
+    if (!std::isfinite(float(A[i])) || !std::isfinite(A[i])) return false;
+    fa += A[i] * A[i];
+  }
+  const double adj[9] = {A[4] * A[8] - A[5] * A[7], A[2] * A[7] - A[1] * A[8], A[1] * A[5] - A[2] * A[4],
+                         A[5] * A[6] - A[3] * A[8], A[0] * A[8] - A[2] * A[6], A[2] * A[3] - A[0] * A[5],
+                         A[3] * A[7] - A[4] * A[6], A[1] * A[6] - A[0] * A[7], A[0] * A[4] - A[1] * A[3]};
+  const double det = A[0] * adj[0] + A[1] * adj[3] + A[2] * adj[6];
+  if (!(det > 0) || !std::isfinite(det)) return false;
+  double fi = 0;
+  for (int i = 0; i < 9; ++i) {
+    inv[i] = adj[i] / det;
+    if (!std::isfinite(float(inv[i]))) return false;
+    fi += inv[i] * inv[i];
+  }
+  const double k = std::sqrt(fa) * std::sqrt(fi);
+  if (cond) *cond = k;
+  return k <= kAffineCond;
+}
+
 Xf compose_translate(const Xf &x, const double off[3]) {
   Xf r = x;
+  if (x.affine) {  // b += A off (both ends of a moving placement)
+    double d[3];
+    mat_vec(x.A, off, d);
+    for (int a = 0; a < 3; ++a) {
+      r.t[a] = x.t[a] + d[a];
+      if (x.moving) r.t1[a] = x.t1[a] + d[a];
+    }
+    r.trans = true;
+    return r;
+  }
   const double th = x.theta * M_PI / 180.0, c = std::cos(th), sn = std::sin(th);
   r.t[0] = x.t[0] + (c * off[0] + sn * off[2]);
   r.t[1] = x.t[1] + off[1];
@@ -187,8 +252,35 @@ void motion_ends(const Xf &x, float o0[3], float o1[3]) {
 }
 Xf compose_rotate(const Xf &x, double angle) {
   Xf r = x;
+  if (x.affine) {  // A = A Ry
+    double R[9];
+    ry_matrix(angle, R);
+    mat_mul(x.A, R, r.A);
+    return r;
+  }
   r.theta = x.theta + angle;
   r.rot = true;
+  return r;
+}
+
+// rt_nw_transform (m, row-major 3x4) under x: b += A m_b, then A = A m_A.  The
+// first one of a chain takes A from the rotations composed so far.
+Xf compose_transform(const Xf &x, const double m[12]) {
+  Xf r = x;
+  if (!x.affine) {
+    ry_matrix(x.rot ? x.theta : 0.0, r.A);
+    r.affine = true;
+  }
+  const double mb[3] = {m[3], m[7], m[11]}, mA[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+  double d[3], P[9];
+  mat_vec(r.A, mb, d);
+  for (int a = 0; a < 3; ++a) {
+    r.t[a] += d[a];
+    if (x.moving) r.t1[a] += d[a];
+  }
+  mat_mul(r.A, mA, P);
+  for (int i = 0; i < 9; ++i) r.A[i] = P[i];
+  r.trans = true;
   return r;
 }
 
@@ -246,11 +338,23 @@ Bounds local_bounds(const SNode &n, int32_t kind) {
 }
 
 Bounds world_bounds(const Bounds &lb, const Xf &x) {
-  if (!x.rot && !x.trans) return lb;
+  if (!x.affine && !x.rot && !x.trans) return lb;
   Bounds b;
   for (int a = 0; a < 3; ++a) {
     b.lo[a] = INFINITY;
     b.hi[a] = -INFINITY;
+  }
+  if (x.affine) {  // the eight corners through (A, t)
+    for (int i = 0; i < 8; ++i) {
+      const double p[3] = {(i & 1) ? lb.hi[0] : lb.lo[0], (i & 2) ? lb.hi[1] : lb.lo[1], (i & 4) ? lb.hi[2] : lb.lo[2]};
+      double q[3];
+      mat_vec(x.A, p, q);
+      for (int a = 0; a < 3; ++a) {
+        b.lo[a] = std::min(b.lo[a], q[a] + x.t[a]);
+        b.hi[a] = std::max(b.hi[a], q[a] + x.t[a]);
+      }
+    }
+    return b;
   }
   const double th = x.theta * M_PI / 180.0, c = std::cos(th), sn = std::sin(th);
   for (int i = 0; i < 8; ++i) {
@@ -318,6 +422,55 @@ struct Flattener {
     }
   }
 
+  // A triangle of an affine placement (only triangles stand under a shared
+  // handle): the flat view cannot express its row, so the triangle appears
+  // baked — vertices float(A v + b(T)) from the double vertices, no Inst, the
+  // attribute normals normalize(A^-T n) (rtmi_nw.h rt_nw_transform).
+  void emit_baked(int32_t id, const Xf &x) {
+    const SNode &n = s->nodes[id];
+    double b[3] = {x.t[0], x.t[1], x.t[2]};
+    if (x.moving) {
+      float o0[3], o1[3], ot[3];
+      motion_ends(x, o0, o1);
+      motion_offset(o0, o1, float(x.time0), float(x.time1), time, ot);
+      for (int a = 0; a < 3; ++a) b[a] = ot[a];
+    }
+    SNode w = n;
+    for (int v = 0; v < 3; ++v) {
+      double q[3];
+      mat_vec(x.A, &n.g[3 * v], q);
+      for (int a = 0; a < 3; ++a) w.g[3 * v + a] = q[a] + b[a];
+    }
+    Obj o{};
+    store_geom(o, w);
+    o.kind = n.kind;
+    o.mat = n.mat;
+    o.inst = -1;
+    o.aux = 0;
+    s->flat_obj.push_back(o);
+    s->flat_src.push_back(id);
+    s->flat_attr.push_back(n.attr);
+    s->flat_bounds.push_back(local_bounds(w, n.kind));
+    if (n.attr < 0) return;
+    TriAttr ta = s->attr[size_t(n.attr)];
+    double inv[9];
+    if ((ta.flags & 1) && affine_inverse(x.A, inv)) {
+      for (int v = 0; v < 3; ++v) {  // A^-T n: the inverse read by columns
+        double w3[3], l2 = 0;
+        for (int j = 0; j < 3; ++j) {
+          w3[j] = inv[j] * ta.n[3 * v] + inv[3 + j] * ta.n[3 * v + 1] + inv[6 + j] * ta.n[3 * v + 2];
+          l2 += w3[j] * w3[j];
+        }
+        const double il = l2 > 0 ? 1.0 / std::sqrt(l2) : 0.0;
+        for (int j = 0; j < 3; ++j) ta.n[3 * v + j] = float(w3[j] * il);
+      }
+    }
+    baked_attr.push_back(ta);
+    baked_of.push_back(int32_t(s->flat_obj.size()) - 1);
+  }
+  std::vector<TriAttr> baked_attr;  // the baked attribute records and the flattened objects they belong to
+  std::vector<int32_t> baked_of;
+
   void emit(int32_t id, Xf x, int depth) {
     if (err) return;
     if (depth > 64) {
@@ -327,6 +480,10 @@ struct Flattener {
     const SNode &n = s->nodes[id];
     switch (n.type) {
       case kPrim: {
+        if (x.affine) {
+          emit_baked(id, x);
+          return;
+        }
         Obj o{};
         store_geom(o, n);
         o.kind = n.kind;
@@ -345,8 +502,21 @@ struct Flattener {
       case kTranslate: emit(n.child, compose_translate(x, n.off), depth + 1); return;
       case kRotate: emit(n.child, compose_rotate(x, n.angle), depth + 1); return;
       case kMove: emit(n.child, compose_move(x, n), depth + 1); return;
+      case kTransform: emit(n.child, compose_transform(x, n.g), depth + 1); return;
       case kShared: {  // the flat view is the expansion; the placement is remembered for the device scene
         const int32_t first = int32_t(s->flat_obj.size());
+        if (x.affine) {  // the composite map obeys rt_nw_transform's bound, and its offsets are floats
+          double inv[9];
+          bool ok = affine_inverse(x.A, inv);
+          for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(float(x.t[a])) && (!x.moving || std::isfinite(float(x.t1[a])));
+          if (!ok) {
+            err = set_error(RT_EINVAL,
+                            "rt_nw: placement %d (shared handle %d): its composite affine map is not finite, not orientation "
+                            "preserving or beyond the conditioning bound %g on |A|_F |A^-1|_F",
+                            int(s->flat_place.size()), id, kAffineCond);
+            return;
+          }
+        }
         emit(n.child, x, depth + 1);
         if (!err) s->flat_place.push_back(rt_nw_scene::Place{id, first, int32_t(s->flat_obj.size()) - first, x});
         return;
@@ -392,9 +562,20 @@ int flatten(rt_nw_scene *s, const float *time = nullptr) {
   s->flat_bounds.clear();
   s->flat_inst.clear();
   s->flat_place.clear();
+  s->flat_attr_view.clear();
+  s->flat_attr_pub.clear();
   Flattener f{s, {}, RT_OK, s->flat_time};
   for (int32_t id : s->world) f.emit(id, Xf{}, 0);
   if (f.err) return f.err;
+  if (!f.baked_attr.empty()) {
+    if (s->attr.size() + f.baked_attr.size() >= (size_t(1) << 27)) return set_error(RT_EINVAL, "rt_nw: too many attribute records");
+    s->flat_attr_view = s->attr;
+    s->flat_attr_pub = s->flat_attr;
+    for (size_t i = 0; i < f.baked_attr.size(); ++i) {
+      s->flat_attr_pub[size_t(f.baked_of[i])] = int32_t(s->flat_attr_view.size());
+      s->flat_attr_view.push_back(f.baked_attr[i]);
+    }
+  }
   // twins: an object that is also a medium's boundary (the same primitive
   // under the same transform, e.g. the final scene's glass sphere and its
   // blue interior, main.cu:386-391) is hidden where that medium hits
@@ -641,6 +822,14 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
     std::vector<Bounds> lb;       // per triangle j, local space
     std::vector<int32_t> tris;    // the j that are not collinear
     Bounds box;                   // their union
+    double reach = 0;             // the farthest a local ray of one of its affine placements starts (0: none)
+  };
+  // triangle k of the flat view in its mesh's local space: the flattened record
+  // itself, except under an affine placement, whose flat view is baked
+  auto local_obj = [&](int32_t k) {
+    Obj o = s->flat_obj[size_t(k)];
+    if (o.kind == kTriangle) Flattener::store_geom(o, s->nodes[size_t(s->flat_src[size_t(k)])]);
+    return o;
   };
   std::vector<MeshBuild> mb;
   std::vector<char> placed;
@@ -661,7 +850,7 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
         }
         m.lb.resize(size_t(p.count));
         for (int32_t j = 0; j < p.count; ++j) {
-          const Obj &o = s->flat_obj[size_t(p.first + j)];
+          const Obj o = local_obj(p.first + j);
           if (o.kind != kTriangle) return set_error(RT_EINVAL, "rt_nw: shared geometry holds a non-triangle");
           m.lb[size_t(j)] = local_bounds(s->nodes[size_t(s->flat_src[size_t(p.first + j)])], kTriangle);
           if (collinear_triangle(o)) continue;  // never hit: keeps its index j, joins no BVH
@@ -760,6 +949,39 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       own = std::max(own, std::max(std::fabs(bounds[k].lo[a]), std::fabs(bounds[k].hi[a])));
     margin[k] = 1e-3 * (1.0 + own) + 1e-6 * scale;
   }
+  // Affine placements (DESIGN.md §9 "Affine placements"): the kernels meet the
+  // mesh under float(A^-1), and a local ray formed in float, so the surface
+  // they see is displaced from A v + b by up to ~2^-22 k (|q| + t |d|) with k =
+  // |A|_F |A^-1|_F <= kAffineCond and q the ray origin seen from b.  The own
+  // scale takes the box's extent about b, and 4e-6 k of the scene's scale and
+  // |b| joins the margin.  The local ray starts up to |A^-1|_F (sqrt 3 scale +
+  // |b|) from the mesh's origin: the mesh's bottom-level margins take that reach
+  // where the scene's scale stands for the other placements.
+  for (int pi = 0; pi < n_place; ++pi) {
+    const Xf &x = places[size_t(pi)].x;
+    MeshBuild &m = mb[size_t(out.place_mesh[size_t(pi)])];
+    if (!x.affine || m.tris.empty()) continue;
+    double inv[9], cond = 0, fi = 0, bmax = 0, ext = 0;
+    if (!affine_inverse(x.A, inv, &cond)) return set_error(RT_EINVAL, "rt_nw: placement %d: bad affine map", pi);
+    for (int i = 0; i < 9; ++i) fi += inv[i] * inv[i];
+    for (int a = 0; a < 3; ++a) {
+      bmax = std::max(bmax, std::fabs(x.t[a]));
+      if (!x.moving) continue;
+      for (double tm : {0.0, 1.0})
+        bmax = std::max(bmax, std::fabs(x.t[a] + (tm - x.time0) / (x.time1 - x.time0) * (x.t1[a] - x.t[a])));
+    }
+    for (int i = 0; i < 8; ++i) {
+      const double p[3] = {(i & 1) ? m.box.hi[0] : m.box.lo[0], (i & 2) ? m.box.hi[1] : m.box.lo[1], (i & 4) ? m.box.hi[2] : m.box.lo[2]};
+      double q[3];
+      mat_vec(x.A, p, q);
+      for (int a = 0; a < 3; ++a) ext = std::max(ext, std::fabs(q[a]));
+    }
+    const int k = n_all + pi;
+    double own = ext;
+    for (int a = 0; a < 3; ++a) own = std::max(own, std::max(std::fabs(bounds[size_t(k)].lo[a]), std::fabs(bounds[size_t(k)].hi[a])));
+    margin[size_t(k)] = 1e-3 * (1.0 + own) + 1e-6 * scale + 4e-6 * cond * (std::sqrt(3.0) * scale + bmax);
+    m.reach = std::max(m.reach, std::sqrt(fi) * (std::sqrt(3.0) * scale + bmax));
+  }
   std::vector<char> solo;
   if (n_place > 0) {
     solo.assign(size_t(n_ext), 0);
@@ -781,6 +1003,7 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
     if (m.tris.empty()) continue;
     double lscale = scale;
     for (int a = 0; a < 3; ++a) lscale = std::max(lscale, std::max(std::fabs(m.box.lo[a]), std::fabs(m.box.hi[a])));
+    lscale = std::max(lscale, m.reach);  // (0 without an affine placement: today's margins)
     std::vector<double> lcost(m.lb.size(), 1.5), lmargin(m.lb.size(), 0.0);
     for (int32_t j : m.tris) {
       double own = 0;
@@ -801,7 +1024,7 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       out.bnodes.push_back(nd);
     }
     for (int32_t j : lb.order) {
-      Obj o = s->flat_obj[size_t(m.first + j)];
+      Obj o = local_obj(m.first + j);
       o.inst = -1;
       o.aux = 0;
       out.pool.push_back(o);
@@ -827,6 +1050,7 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
   out.place_slot.assign(size_t(n_place), -1);
   out.inst = s->flat_inst;
   out.n_moving = 0;
+  out.n_affine = 0;
   for (int k = 0; k < n; ++k) {
     if (bvh.order[k] >= n_all) {  // a placement's record (rtmi_nw_types.h kInstance)
       const int pi = bvh.order[k] - n_all;
@@ -840,7 +1064,32 @@ int build_device_scene(rt_nw_scene *s, DeviceScene &out) {
       o.mat = 0;
       o.inst = s->flat_obj[size_t(p.first)].inst;  // every object of the expansion carries the same one
       o.aux = 0;
-      if (p.x.moving) {
+      if (p.x.affine) {
+        // an affine placement (rtmi_nw_types.h AffInst): two Inst rows of its
+        // own behind the flat view's hold float(A^-1) and o0; aux bit 1 marks
+        // it, and a moving one keeps the motion words where they are
+        AffInst ai{};
+        double inv[9];
+        (void)affine_inverse(p.x.A, inv);  // (checked when the world was flattened)
+        float o1[3];
+        for (int i = 0; i < 9; ++i) ai.m[i] = float(inv[i]);
+        motion_ends(p.x, ai.off, o1);
+        ai.flags = 4;
+        Inst rows[2];
+        std::memcpy(rows, &ai, sizeof ai);
+        out.inst.push_back(rows[0]);
+        out.inst.push_back(rows[1]);
+        o.inst = int32_t(out.inst.size()) - 2;
+        o.aux = 2;
+        ++out.n_affine;
+        if (p.x.moving) {
+          for (int a = 0; a < 3; ++a) o.g1[1 + a] = o1[a];
+          o.g2[0] = float(p.x.time1);
+          o.g2[1] = float(p.x.time0);
+          o.aux = 3;
+          ++out.n_moving;
+        }
+      } else if (p.x.moving) {
         // the flat view's Inst is the placement at one instant; the device takes
         // an Inst of its own with o0 and the motion in the record's free words
         // (rtmi_nw_types.h kInstance), and forms off(time) per ray
@@ -1430,7 +1679,8 @@ RTMI_EXPORT int rt_nw_load_obj(rt_nw_scene *s, const char *path, int32_t mat, in
 // the mesh's lambertian or metal material.
 namespace {
 int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb, int32_t w, int32_t h,
-              double aspect, rt_nw_camera *cam, int32_t *n_tris, int32_t copies = 1, const double *move = nullptr) {
+              double aspect, rt_nw_camera *cam, int32_t *n_tris, int32_t copies = 1, const double *move = nullptr,
+              bool tumble = false) {
   if (!s || !path || !cam || !(aspect > 0) || !mesh_flags_ok(flags)) return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: bad argument");
   if (move && !(std::isfinite(float(move[0])) && std::isfinite(float(move[1])) && std::isfinite(float(move[2]))))
     return set_error(RT_EINVAL, "rt_nw_scene_obj_stage: move vector not finite");
@@ -1470,7 +1720,32 @@ int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags
   if (rc) return rc;
   chk(rt_nw_world_add(s, ground));
   const double still[3] = {0, 0, 0};
-  if (copies == 1 && move) {  // one moving placement of the model as a shared mesh
+  // --obj-tumble: copy q as an affine placement (rt_nw_transform) at its field
+  // position — uniform scale 0.75 + 0.25 sin(2.9 q), turned 37 q degrees about
+  // normalize(sin 1.3 q, 1, cos 0.7 q), lifted until the lowest corner of its
+  // transformed stage box [-1, 1] x [0, 2] x [-1, 1] stands on y = 0
+  auto tumbled = [&](int shared, int q, const double off[3]) {
+    const double sc = 0.75 + 0.25 * std::sin(2.9 * q), th = 37.0 * q * M_PI / 180.0;
+    double ax[3] = {std::sin(1.3 * q), 1.0, std::cos(0.7 * q)};
+    const double al = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+    for (double &v : ax) v /= al;
+    const double c = std::cos(th), sn = std::sin(th), k1 = 1.0 - c;
+    const double R[9] = {c + k1 * ax[0] * ax[0],          k1 * ax[0] * ax[1] - sn * ax[2], k1 * ax[0] * ax[2] + sn * ax[1],
+                         k1 * ax[1] * ax[0] + sn * ax[2], c + k1 * ax[1] * ax[1],          k1 * ax[1] * ax[2] - sn * ax[0],
+                         k1 * ax[2] * ax[0] - sn * ax[1], k1 * ax[2] * ax[1] + sn * ax[0], c + k1 * ax[2] * ax[2]};
+    double low = INFINITY;
+    for (int i = 0; i < 8; ++i) {
+      const double p[3] = {(i & 1) ? 1.0 : -1.0, (i & 2) ? 2.0 : 0.0, (i & 4) ? 1.0 : -1.0};
+      low = std::min(low, sc * (R[3] * p[0] + R[4] * p[1] + R[5] * p[2]));
+    }
+    const double m[12] = {sc * R[0], sc * R[1], sc * R[2], off[0], sc * R[3], sc * R[4], sc * R[5], off[1] - low,
+                          sc * R[6], sc * R[7], sc * R[8], off[2]};
+    return rt_nw_transform(s, shared, m);
+  };
+  if (copies == 1 && tumble) {
+    const int placed = chk(tumbled(chk(rt_nw_shared(s, mesh)), 0, still));
+    chk(rt_nw_world_add(s, move ? chk(rt_nw_move(s, placed, still, move, 0.0, 1.0)) : placed));
+  } else if (copies == 1 && move) {  // one moving placement of the model as a shared mesh
     chk(rt_nw_world_add(s, chk(rt_nw_move(s, chk(rt_nw_shared(s, mesh)), still, move, 0.0, 1.0))));
   } else if (copies == 1) {
     chk(rt_nw_world_add(s, mesh));
@@ -1485,7 +1760,7 @@ int obj_stage(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags
         const int q = i * copies + k;
         const double off[3] = {3.0 * (i - 0.5 * (copies - 1)) + 0.4 * std::sin(1.7 * q), 0.0,
                                3.0 * (k - 0.5 * (copies - 1)) + 0.4 * std::cos(2.3 * q)};
-        const int placed = chk(rt_nw_translate(s, chk(rt_nw_rotate_y(s, shared, 37.0 * q)), off));
+        const int placed = tumble ? chk(tumbled(shared, q, off)) : chk(rt_nw_translate(s, chk(rt_nw_rotate_y(s, shared, 37.0 * q)), off));
         chk(rt_nw_world_add(s, move ? chk(rt_nw_move(s, placed, still, move, 0.0, 1.0)) : placed));
         if (rc) return rc;
       }
@@ -1525,12 +1800,19 @@ RTMI_EXPORT int rt_nw_scene_obj_stage_moving(rt_nw_scene *s, const char *path, i
   return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris, copies, move);
 }
 
+RTMI_EXPORT int rt_nw_scene_obj_stage_tumbled(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags,
+                                              const uint8_t *rgb, int32_t w, int32_t h, int32_t copies, const double *move,
+                                              double aspect, rt_nw_camera *cam, int32_t *n_tris) {
+  return obj_stage(s, path, mat_kind, flags, rgb, w, h, aspect, cam, n_tris, copies, move, true);
+}
+
 RTMI_EXPORT int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex) {
   if (!s || !valid_node(s, boundary) || !valid_tex(s, tex) || !(density > 0))
     return set_error(RT_EINVAL, "rt_nw_constant_medium: bad argument");
   {  // a triangle (under any translate / rotate_y chain) bounds no volume
     int32_t b = boundary;
-    while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate || s->nodes[b].type == kMove))
+    while (valid_node(s, b) && (s->nodes[b].type == kTranslate || s->nodes[b].type == kRotate || s->nodes[b].type == kMove ||
+                                s->nodes[b].type == kTransform))
       b = s->nodes[b].child;
     if (valid_node(s, b) && ((s->nodes[b].type == kPrim && s->nodes[b].kind == kTriangle) || s->nodes[b].type == kShared))
       return set_error(RT_EUNSUPPORTED, "rt_nw_constant_medium: a triangle cannot be a medium's boundary");
@@ -1619,9 +1901,11 @@ RTMI_EXPORT int rt_nw_move(rt_nw_scene *s, int32_t object, const double offset0[
   for (int a = 0; a < 3; ++a)
     if (!std::isfinite(float(offset0[a])) || !std::isfinite(float(offset1[a])))
       return set_error(RT_EINVAL, "rt_nw_move: offset not finite");
-  // under it: one shared handle, optionally under translate / rotate_y nodes
+  // under it: one shared handle, optionally under translate / rotate_y / transform nodes
   int32_t b = object;
-  for (int depth = 0; s->nodes[size_t(b)].type == kTranslate || s->nodes[size_t(b)].type == kRotate; ++depth) {
+  for (int depth = 0; s->nodes[size_t(b)].type == kTranslate || s->nodes[size_t(b)].type == kRotate ||
+                      s->nodes[size_t(b)].type == kTransform;
+       ++depth) {
     if (depth > 64) return set_error(RT_EINVAL, "rt_nw_move: object nesting deeper than 64 (a cycle?)");
     b = s->nodes[size_t(b)].child;
   }
@@ -1639,6 +1923,42 @@ RTMI_EXPORT int rt_nw_move(rt_nw_scene *s, int32_t object, const double offset0[
   n.time1 = time1;
   ++s->n_moves;
   return add_node(s, n);
+}
+
+RTMI_EXPORT int rt_nw_transform(rt_nw_scene *s, int32_t object, const double m[12]) {
+  if (!s || !m || !valid_node(s, object)) return set_error(RT_EINVAL, "rt_nw_transform: bad argument");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(m[i]) || !std::isfinite(float(m[i]))) return set_error(RT_EINVAL, "rt_nw_transform: entry %d not finite as a float", i);
+  const double A[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+  double inv[9];
+  if (!affine_inverse(A, inv))
+    return set_error(RT_EINVAL,
+                     "rt_nw_transform: the 3x3 part must have a positive determinant (no mirror) and |A|_F |A^-1|_F <= %g",
+                     kAffineCond);
+  // under it: one shared handle, optionally under translate / rotate_y /
+  // transform nodes and at most one move (rt_nw_move sees to that)
+  int32_t b = object;
+  for (int depth = 0; s->nodes[size_t(b)].type == kTranslate || s->nodes[size_t(b)].type == kRotate ||
+                      s->nodes[size_t(b)].type == kTransform || s->nodes[size_t(b)].type == kMove;
+       ++depth) {
+    if (depth > 64) return set_error(RT_EINVAL, "rt_nw_transform: object nesting deeper than 64 (a cycle?)");
+    b = s->nodes[size_t(b)].child;
+  }
+  if (s->nodes[size_t(b)].type != kShared)
+    return set_error(RT_EUNSUPPORTED, "rt_nw_transform: only a placement of a shared mesh (rt_nw_shared) takes an affine map");
+  SNode n;
+  n.type = kTransform;
+  n.child = object;
+  for (int i = 0; i < 12; ++i) n.g[i] = m[i];
+  return add_node(s, n);
+}
+
+RTMI_EXPORT int rt_nw_scene_affine_stats(rt_nw_scene *s, int32_t out[2]) {
+  if (!s || !out) return set_error(RT_EINVAL, "rt_nw_scene_affine_stats: null");
+  if (int rc = flatten(s)) return rc;
+  out[0] = out[1] = 0;
+  for (const rt_nw_scene::Place &p : s->flat_place) ++out[p.x.affine ? 0 : 1];
+  return RT_OK;
 }
 
 RTMI_EXPORT int rt_nw_scene_motion_stats(rt_nw_scene *s, int32_t out[2]) {
@@ -1702,9 +2022,11 @@ RTMI_EXPORT int rt_nw_scene_flat_at(rt_nw_scene *s, double time, rt_nw_flat *out
 RTMI_EXPORT int rt_nw_scene_flat_attr(rt_nw_scene *s, int32_t *n_attr, const float **attr, const int32_t **attr_of_obj) {
   if (!s || !n_attr || !attr || !attr_of_obj) return set_error(RT_EINVAL, "null");
   if (int rc = flatten(s)) return rc;
-  *n_attr = int32_t(s->attr.size());
-  *attr = reinterpret_cast<const float *>(s->attr.data());
-  *attr_of_obj = s->flat_attr.data();
+  const bool baked = !s->flat_attr_pub.empty();  // an affine placement with attribute records
+  const std::vector<TriAttr> &rec = baked ? s->flat_attr_view : s->attr;
+  *n_attr = int32_t(rec.size());
+  *attr = reinterpret_cast<const float *>(rec.data());
+  *attr_of_obj = baked ? s->flat_attr_pub.data() : s->flat_attr.data();
   return RT_OK;
 }
 

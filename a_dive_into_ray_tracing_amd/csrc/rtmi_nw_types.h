@@ -27,7 +27,10 @@ enum ObjKind : int32_t {
                       //                     inst = the placement's Inst or -1 (DESIGN.md §9 "Shared meshes").
                       //                     A moving placement (rt_nw_move): aux = 1, its Inst holds o0,
                       //                     g1[1..3] = o1, g2 = {time1, time0} (DevObj: t1 = time1, mat = the bits
-                      //                     of time0; a static placement's are zero)
+                      //                     of time0; a static placement's are zero).
+                      //                     An affine placement (rt_nw_transform): aux bit 1 (aux = 2, moving 3);
+                      //                     inst = the first of two Inst rows read as one AffInst, whose off is
+                      //                     o0; the motion words as above
 };
 
 // material kinds = RT_NW_* (rtmi_nw.h)
@@ -67,6 +70,13 @@ struct Inst {  // 32 B; world = translate(rotate_y(local)) (hittable.h:49-189)
   float off[3];    // composed translation
   int32_t flags;   // bit 0 rotation present, bit 1 translation present
   int32_t pad[2];
+};
+// An affine placement's two Inst rows (rt_nw_transform, TRI = 5): local = m (world - off)
+struct AffInst {  // 64 B
+  float m[9];      // float(A^-1), row-major
+  float off[3];    // float(b); a moving placement's o0
+  int32_t flags;   // 4
+  int32_t pad[3];
 };
 // The translation of a moving placement (rt_nw_move) at ray time T — the one
 // place it is written, for the host's flat view (rt_nw_scene_flat_at) and the
@@ -112,6 +122,7 @@ constexpr int kNodeLeafMax = 4;
 
 static_assert(sizeof(Obj) == 64, "Obj layout");
 static_assert(sizeof(Inst) == 32, "Inst layout");
+static_assert(sizeof(AffInst) == 2 * sizeof(Inst), "AffInst layout");
 
 }  // namespace nw
 }  // namespace rtmi

@@ -198,6 +198,26 @@ class Scene:
         translate / rotate_y nodes."""
         return _id(load().rt_nw_move(self._h, obj, _v3(off0), _v3(off1), float(t0), float(t1)), "rt_nw_move")
 
+    def transform(self, obj, m):
+        """A placement node with the affine map world = A local + b (rt_nw_transform).
+        m: 3 x 4 (A | b), or 4 x 4 with the last row 0 0 0 1.  `obj`: one shared
+        handle under translate / rotate_y / transform nodes and at most one move."""
+        a = np.asarray(m, np.float64)
+        if a.shape == (4, 4):
+            if not np.array_equal(a[3], [0.0, 0.0, 0.0, 1.0]):
+                raise ValueError("Scene.transform: the last row of a 4 x 4 matrix must be 0 0 0 1")
+            a = a[:3]
+        if a.shape != (3, 4):
+            raise ValueError("Scene.transform: a 3 x 4 or 4 x 4 matrix")
+        a = np.ascontiguousarray(a)
+        return _id(load().rt_nw_transform(self._h, obj, a.ctypes.data_as(C.POINTER(C.c_double))), "rt_nw_transform")
+
+    def affine_stats(self):
+        """(affine placements reached from the world, other placements) (rt_nw_scene_affine_stats)."""
+        v = (C.c_int32 * 2)()
+        check(load().rt_nw_scene_affine_stats(self._h, v), "rt_nw_scene_affine_stats")
+        return v[0], v[1]
+
     def motion_stats(self):
         """(moving placements reached from the world, static placements) (rt_nw_scene_motion_stats)."""
         v = (C.c_int32 * 2)()
@@ -285,7 +305,21 @@ def _mesh_flags(smooth, uv, gen_normals):
     return (1 if smooth else 0) | (2 if uv else 0) | (4 if gen_normals else 0)
 
 
-def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None, copies=1, move=None):
+def affine(scale=1.0, axis=(0, 1, 0), angle=0.0, translate=(0, 0, 0)):
+    """The 3 x 4 matrix of Scene.transform for: scale (a scalar or three values,
+    along x, y, z), then a rotation of `angle` degrees about `axis`, then the
+    translation."""
+    sc = np.broadcast_to(np.asarray(scale, np.float64), (3,))
+    ax = np.asarray(axis, np.float64)
+    ax = ax / np.linalg.norm(ax)
+    th = np.deg2rad(float(angle))
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+    return np.concatenate([R @ np.diag(sc), np.asarray(translate, np.float64).reshape(3, 1)], axis=1)
+
+
+def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=False, texture=None, copies=1, move=None,
+              tumble=False):
     """The scene of `rtmi_nw_render --obj FILE --obj-mat MAT` and its camera:
     (scene, camera, triangle count).  smooth / gen_normals as Scene.load_obj;
     texture (h x w x 3 uint8): the mesh's texture, mapped by the file's vt
@@ -298,6 +332,18 @@ def obj_stage(path, mat="lambertian", aspect=1.0, smooth=False, gen_normals=Fals
     s = Scene()
     cam = RtNwCamera()
     n = C.c_int32()
+    if tumble:  # (`--obj-tumble`: every copy an affine placement, rt_nw_scene_obj_stage_tumbled)
+        if texture is not None:
+            a = np.ascontiguousarray(texture, np.uint8)
+            ptr, ih, iw = a.ctypes.data_as(_u8), a.shape[0], a.shape[1]
+        else:
+            ptr, ih, iw = None, 0, 0
+        check(load().rt_nw_scene_obj_stage_tumbled(s._h, str(path).encode(), kind,
+                                                   _mesh_flags(smooth, texture is not None, gen_normals), ptr, iw, ih,
+                                                   int(copies), None if move is None else _v3(move), float(aspect),
+                                                   C.byref(cam), C.byref(n)),
+              "rt_nw_scene_obj_stage_tumbled")
+        return s, cam, n.value
     if move is not None:
         if texture is not None:
             a = np.ascontiguousarray(texture, np.uint8)
@@ -444,7 +490,7 @@ class NwRenderer:
         return v.value
 
     def scene_tri(self):
-        """Diagnostic: the kernel family of the resident scene, 0..4 (rt_nw_ctx_scene_tri)."""
+        """Diagnostic: the kernel family of the resident scene, 0..5 (rt_nw_ctx_scene_tri)."""
         v = C.c_int32()
         check(load().rt_nw_ctx_scene_tri(self._h, C.byref(v)), "rt_nw_ctx_scene_tri")
         return v.value

@@ -165,6 +165,16 @@ int rt_nw_scene_obj_stage_copies(rt_nw_scene *s, const char *path, int32_t mat_k
 int rt_nw_scene_obj_stage_moving(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
                                  int32_t w, int32_t h, int32_t copies, const double move[3], double aspect,
                                  rt_nw_camera *cam, int32_t *n_tris);
+/* rt_nw_scene_obj_stage_copies with copy q of the field as an affine placement
+ * (rt_nw_transform; `rtmi_nw_render --obj-tumble`): uniform scale 0.75 + 0.25
+ * sin(2.9 q), turned 37 q degrees about normalize(sin 1.3 q, 1, cos 0.7 q), at
+ * its field position, lifted until the lowest corner of its transformed stage
+ * box stands on y = 0.  copies == 1: the model as one such placement (q = 0).
+ * move, when not null: every placement under rt_nw_move as in
+ * rt_nw_scene_obj_stage_moving. */
+int rt_nw_scene_obj_stage_tumbled(rt_nw_scene *s, const char *path, int32_t mat_kind, uint32_t flags, const uint8_t *rgb,
+                                  int32_t w, int32_t h, int32_t copies, const double *move, double aspect,
+                                  rt_nw_camera *cam, int32_t *n_tris);
 int rt_nw_constant_medium(rt_nw_scene *s, int32_t boundary, double density, int32_t tex);
 /* Scattering-distance samples of a medium per ray segment (1..8, default 1):
  * each draws -log(u)/density anew and the last one that lands inside the
@@ -213,6 +223,32 @@ int rt_nw_shared(rt_nw_scene *s, int32_t object);
  * the static scene rt_nw_scene_flat_at(T) describes, bit for bit. */
 int rt_nw_move(rt_nw_scene *s, int32_t object, const double offset0[3], const double offset1[3], double time0,
                double time1);
+/* A placement node with a general affine map, world = A local + b.  m is
+ * row-major 3x4: A = {m[0..2], m[4..6], m[8..10]}, b = {m[3], m[7], m[11]}.  A
+ * new handle, used like rt_nw_translate's.  Only a placement of a shared mesh
+ * takes an affine map: the subtree of `object` must be one rt_nw_shared handle
+ * under any chain of rt_nw_translate, rt_nw_rotate_y, rt_nw_transform and at
+ * most one rt_nw_move node, in any order — a primitive, a group, a medium, a
+ * flattened mesh: RT_EUNSUPPORTED; as a medium's boundary, or under
+ * rt_nw_shared: RT_EUNSUPPORTED.  RT_EINVAL at the call: an entry not finite
+ * as a float; det(A) <= 0 (a singular map, or a mirror: out of scope);
+ * |A|_F |A^-1|_F > 1024 (Frobenius norms; every matrix whose singular values
+ * lie in [1/16, 16] passes).  The same bound holds for a placement's composite
+ * map and is checked wherever the scene is flattened (rt_nw_scene_flat*, the
+ * stats calls, rt_nw_ctx_set_scene): RT_EINVAL naming the placement.
+ * Composition runs in double from the world down, (A, b) starting at (I, 0):
+ * translate(off): b += A off; rotate_y: A = A Ry; transform(m): b += A m_b,
+ * then A = A m_A; a move carries b and b1 side by side.  The kernels take the
+ * world ray into the placement's frame with float(A^-1) and do not renormalise
+ * the direction, so t is the world ray's (DESIGN.md §9 "Affine placements").
+ * A placement whose chain holds no transform node is built exactly as before.
+ * In the flat view an affine placement's triangles appear BAKED: vertices
+ * float(A v + b(T)) from the double vertices, inst = -1, attribute normals
+ * normalize(A^-T n) computed in double and rounded, insertion indices first(p)
+ * + j as always.  For affine placements the flat view is therefore the nearest
+ * static scene, NOT a bit-for-bit expansion: transforming the ray and
+ * transforming the vertices round differently. */
+int rt_nw_transform(rt_nw_scene *s, int32_t object, const double m[12]);
 int rt_nw_world_add(rt_nw_scene *s, int32_t object);
 int rt_nw_set_background(rt_nw_scene *s, double r, double g, double b);
 
@@ -280,6 +316,9 @@ int rt_nw_scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *max_cell, in
  * per placement), top-level BVH nodes}.  Without a placement the first four
  * are zero. */
 int rt_nw_scene_instancing_stats(rt_nw_scene *s, int32_t out[6]);
+/* Host only: {affine placements (a rt_nw_transform in their chain) reached from
+ * the world, other placements}. */
+int rt_nw_scene_affine_stats(rt_nw_scene *s, int32_t out[2]);
 /* Host only: {moving placements (under a rt_nw_move) reached from the world,
  * static placements}. */
 int rt_nw_scene_motion_stats(rt_nw_scene *s, int32_t out[2]);
@@ -351,7 +390,8 @@ int rt_nw_ctx_last_segments(rt_nw_ctx *ctx, uint64_t *segments);
 int rt_nw_ctx_last_kernel(rt_nw_ctx *ctx, int32_t *out4);
 /* Diagnostic: the instantiation family the resident scene renders with — 0 no
  * triangle, 1 triangles, 2 triangles with attribute records, 3 placements of
- * shared meshes, 4 placements of which at least one moves. */
+ * shared meshes, 4 placements of which at least one moves, 5 placements of
+ * which at least one is affine (rt_nw_transform). */
 int rt_nw_ctx_scene_tri(rt_nw_ctx *ctx, int32_t *tri);
 /* Diagnostic: what the last render's kernel walked from LDS, {BVH nodes,
  * object records} (1 / 0; the uniform grid stages the objects, no nodes). */
