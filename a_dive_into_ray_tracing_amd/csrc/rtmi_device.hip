@@ -1715,6 +1715,7 @@ bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, int32_t 
     out.desc.g1[a] = std::fmaf(float(out.desc.n[a]), h, g0);
   }
   out.desc.ncells = int32_t(total);
+  if (!grid_strides(out.desc)) return false;  // (never at <= 128 cells per axis; the walk's 24-bit multiplies rest on it)
   std::vector<std::vector<uint16_t>> lists(static_cast<size_t>(total));
   for (int32_t k : small) {  // ascending scene index
     const double *c = b.cr + 4 * k, R = std::fabs(c[3]) + b.margin(k);
@@ -1944,6 +1945,52 @@ RTMI_EXPORT int rt_ctx_grid_info(rt_ctx *ctx, int32_t *dims3, int32_t *n_refs, i
   if (dims3) for (int a = 0; a < 3; ++a) dims3[a] = ctx->grid.n[a];
   if (n_refs) *n_refs = ctx->grid.nrefs;
   if (lds_bytes) *lds_bytes = int32_t(grid_lds_bytes(2 * ctx->nbig_pairs, ctx->grid.ncells, ctx->grid.nrefs));
+  return RT_OK;
+}
+
+// Validation entry points (host only, no device): the cell-start strides
+// grid_strides gives a grid of n3 cells per axis, or RT_EINVAL where it
+// refuses the grid; and the cell counts and strides of the descriptor
+// build_grid fills for a scene (the split into big and small spheres as in
+// rt_ctx_set_scene), with its origin and cell size (box6, optional).
+RTMI_EXPORT int rt_debug_grid_strides(const int32_t *n3, uint32_t *strides2) {
+  if (!n3 || !strides2) return set_error(RT_EINVAL, "rt_debug_grid_strides: bad argument");
+  GridDesc d{};
+  for (int a = 0; a < 3; ++a) d.n[a] = n3[a];
+  if (!grid_strides(d)) return set_error(RT_EINVAL, "grid of %d x %d x %d cells: over the walk's 24-bit bound", n3[0], n3[1], n3[2]);
+  strides2[0] = d.row_bytes;
+  strides2[1] = d.layer_bytes;
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint32_t *strides2, float *box6) {
+  if (!scene || scene->n <= 0 || !scene->center_radius || !dims3 || !strides2)
+    return set_error(RT_EINVAL, "rt_debug_grid_layout: bad argument");
+  const int n = scene->n;
+  std::vector<float4> g(n, make_float4(0.f, 0.f, 0.f, 0.f));  // (build_grid copies the records; their values do not shape the grid)
+  std::vector<double> rad(n);
+  for (int k = 0; k < n; k++) rad[k] = std::fabs(scene->center_radius[4 * k + 3]);
+  std::vector<double> sorted_r = rad;
+  std::nth_element(sorted_r.begin(), sorted_r.begin() + n / 2, sorted_r.end());
+  const double med = sorted_r[n / 2];
+  std::vector<int32_t> big, small;
+  double scale = 0;
+  for (int k = 0; k < n; k++) {
+    (rad[k] > RTMI_BIG_FACTOR * med ? big : small).push_back(k);
+    for (int a = 0; a < 3; ++a) scale = std::max(scale, std::fabs(scene->center_radius[4 * k + a]) + rad[k]);
+  }
+  BvhBuilder b{scene->center_radius, g, 1e-6 * scale, {}, {}, {}};
+  const int nb_pad = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
+  GridBuild gb;
+  if (small.empty() || !build_grid(b, small, n, nb_pad, gb)) return set_error(RT_EUNSUPPORTED, "no grid for this scene");
+  for (int a = 0; a < 3; ++a) dims3[a] = gb.desc.n[a];
+  strides2[0] = gb.desc.row_bytes;
+  strides2[1] = gb.desc.layer_bytes;
+  if (box6)  // the grid's origin and cell size, as the walk reads them
+    for (int a = 0; a < 3; ++a) {
+      box6[a] = gb.desc.g0[a];
+      box6[3 + a] = gb.desc.h[a];
+    }
   return RT_OK;
 }
 

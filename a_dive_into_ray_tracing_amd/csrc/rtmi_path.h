@@ -451,7 +451,26 @@ struct GridDesc {
   const uint32_t *cells;  // ncells + 1 first-reference indices
   const uint32_t *refs;
   uint32_t cells_off, idx_off;  // in LDS: the cell starts and the slot indices, bytes past the slots
+  // the cell-start table's strides in bytes, 4 n0 and 4 n0 n1 (grid_strides):
+  // the walk forms a cell's address with 24-bit multiplies by these
+  uint32_t row_bytes, layer_bytes;
+  float nm1[3];  // n - 1 as floats: the entry cell's clamp
 };
+
+// The strides of the cell-start table.  The walk multiplies them by cell
+// coordinates with v_mul_u32_u24, which reads 24 bits of each operand: the
+// coordinates must stay below 2^16 and the strides below 2^24, or the grid is
+// refused (false).
+inline bool grid_strides(GridDesc &g) {
+  for (int a = 0; a < 3; ++a)
+    if (g.n[a] < 1 || g.n[a] >= (1 << 16)) return false;
+  const uint64_t row = 4ull * uint64_t(g.n[0]), layer = row * uint64_t(g.n[1]);
+  if (layer >= (1ull << 24)) return false;
+  g.row_bytes = uint32_t(row);
+  g.layer_bytes = uint32_t(layer);
+  for (int a = 0; a < 3; ++a) g.nm1[a] = float(g.n[a] - 1);
+  return true;
+}
 
 struct Accel {
   const SpherePair *big;     // packed pairs of the big spheres (padded like the scene)
@@ -576,7 +595,17 @@ __device__ __forceinline__ uint32_t lds_u16(uint32_t addr) {
 // (v_rcp_f32, ~1 ulp) instead of a correctly rounded division: the
 // structures' margins are ~1e4 times larger than that error, and no hit
 // result depends on it (the sphere tests use the exact inv_a).
+// BY_MAX: the clamp written as copysign(max(|v|, 1e-20), v) — the same
+// operand for every non-NaN v (-0.0 gives -1e-20 either way), one instruction
+// fewer than the compare and select.  A NaN component, which the compare
+// lets through to a NaN inverse, gives max's other operand there, so an
+// inverse of +-1e20: the slab test then treats the axis as parallel instead of
+// comparing NaNs (no ray the renderer forms has one).  Only the one-layer grid
+// walk asks for it: in the general walk's kernels the same form spills one to
+// two more VGPRs (profiles/r08/prologue/kernel_resources.txt).
+template <bool BY_MAX = false>
 __device__ __forceinline__ float safe_inv(float v) {
+  if constexpr (BY_MAX) return __builtin_amdgcn_rcpf(__builtin_copysignf(__builtin_fmaxf(__builtin_fabsf(v), 1e-20f), v));
   const float c = __builtin_fabsf(v) < 1e-20f ? __builtin_copysignf(1e-20f, v) : v;
   return __builtin_amdgcn_rcpf(c);
 }
@@ -779,7 +808,7 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
   unsigned long long tp2 = tp1;
 #endif
   const GridDesc &G = rtmi_grid_desc;  // (stage_grid)
-  const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
+  const float ix = safe_inv<FLAT_Y>(d.x), iy = safe_inv<FLAT_Y>(d.y), iz = safe_inv<FLAT_Y>(d.z);
   const float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
   // the grid box, clipped to [0, t_max]
   const float bx0 = __builtin_fmaf(G.g0[0], ix, ox), bx1 = __builtin_fmaf(G.g1[0], ix, ox);
@@ -791,14 +820,20 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
                                      __builtin_fminf(__builtin_fmaxf(bz0, bz1), t_max));
   if (tnear <= tfar) {
     const uint32_t cells = base + G.cells_off;
-    // entry cell: the cell of o + tnear*d, clamped into the grid
+    // entry cell: the cell of o + tnear*d, clamped into the grid.
+    // The floored coordinate is clamped as a float (one v_med3_f32), and t0
+    // and kmax are formed from that float: it is an integer below 2^16, so
+    // c + 1 and n - 1 - c are exact in float and equal the conversions of the
+    // integer forms bit for bit.  One conversion per axis remains, for the
+    // address.  (A NaN coordinate: the integer conversion gave cell 0; med3
+    // gives the smaller bound, 0, as well.)
     auto cell_of = [&](float p, int ax) {
-      const int c = int(__builtin_floorf((p - G.g0[ax]) * G.inv_h[ax]));
-      return c < 0 ? 0 : (c >= G.n[ax] ? G.n[ax] - 1 : c);
+      return __builtin_amdgcn_fmed3f(__builtin_floorf((p - G.g0[ax]) * G.inv_h[ax]), 0.0f, G.nm1[ax]);
     };
-    const int cx = cell_of(__builtin_fmaf(tnear, d.x, o.x), 0);
-    const int cy = FLAT_Y ? 0 : cell_of(__builtin_fmaf(tnear, d.y, o.y), 1);
-    const int cz = cell_of(__builtin_fmaf(tnear, d.z, o.z), 2);
+    const float fx = cell_of(__builtin_fmaf(tnear, d.x, o.x), 0);
+    const float fy = FLAT_Y ? 0.0f : cell_of(__builtin_fmaf(tnear, d.y, o.y), 1);
+    const float fz = cell_of(__builtin_fmaf(tnear, d.z, o.z), 2);
+    const int cx = int(fx), cy = int(fy), cz = int(fz);
     // Per axis: after k steps on it the current cell's far face lies at
     // t = fma(k, dt, t0) (t0 the entry cell's far face, dt = h/|d_axis|), and
     // the walk leaves the grid when it would step past kmax.  (Only which
@@ -809,25 +844,29 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
     // The step direction comes from the culling inverse, not from d: safe_inv
     // gives -0.0 the inverse -1e20, so `d >= 0` (true for -0.0) would pick the
     // far face on the wrong side and step into cells the ray never enters.
-    auto axis = [&](float inv, float oo, int c, int ax, float &t0, float &dt, float &kmax) {
+    auto axis = [&](float inv, float oo, float cf, int ax, float &t0, float &dt, float &kmax) {
       const bool pos = inv >= 0.0f;
-      t0 = __builtin_fmaf(__builtin_fmaf(float(c + (pos ? 1 : 0)), G.h[ax], G.g0[ax]), inv, oo);
+      t0 = __builtin_fmaf(__builtin_fmaf(pos ? cf + 1.0f : cf, G.h[ax], G.g0[ax]), inv, oo);
       dt = __builtin_fabsf(G.h[ax] * inv);
-      kmax = float(pos ? G.n[ax] - 1 - c : c);
+      kmax = pos ? G.nm1[ax] - cf : cf;
     };
-    axis(ix, ox, cx, 0, t0x, dtx, kmx);
+    axis(ix, ox, fx, 0, t0x, dtx, kmx);
     if constexpr (FLAT_Y) {  // the one layer's far y face (axis() at c = 0, no steps)
       t0y = __builtin_fmaf(__builtin_fmaf(iy >= 0.0f ? 1.0f : 0.0f, G.h[1], G.g0[1]), iy, oy);
       dty = kmy = 0.0f;
     } else {
-      axis(iy, oy, cy, 1, t0y, dty, kmy);
+      axis(iy, oy, fy, 1, t0y, dty, kmy);
     }
-    axis(iz, oz, cz, 2, t0z, dtz, kmz);
+    axis(iz, oz, fz, 2, t0z, dtz, kmz);
     float kx = 0.0f, ky = 0.0f, kz = 0.0f, tnx = t0x, tny = t0y, tnz = t0z;
-    // the LDS address of the current cell's start, stepped by 4 x the cell step
-    uint32_t cell = cells + 4u * uint32_t(cx + G.n[0] * (cy + G.n[1] * cz));
-    const int dcx = ix >= 0.0f ? 4 : -4, dcy = iy >= 0.0f ? 4 * G.n[0] : -4 * G.n[0];
-    const int dcz = iz >= 0.0f ? 4 * G.n[0] * G.n[1] : -4 * G.n[0] * G.n[1];
+    // the LDS address of the current cell's start, stepped by 4 x the cell step:
+    // by the descriptor's byte strides and 24-bit multiplies (grid_strides);
+    // the one-layer walk has cy = 0 and no y step
+    uint32_t cell = cells + 4u * uint32_t(cx) + __umul24(uint32_t(cz), G.layer_bytes);
+    if constexpr (!FLAT_Y) cell += __umul24(uint32_t(cy), G.row_bytes);
+    const int dcx = ix >= 0.0f ? 4 : -4;
+    const int dcy = FLAT_Y ? 0 : (iy >= 0.0f ? int(G.row_bytes) : -int(G.row_bytes));
+    const int dcz = iz >= 0.0f ? int(G.layer_bytes) : -int(G.layer_bytes);
 #if RTMI_TRACE_PHASES
     tp2 = __builtin_amdgcn_s_memtime();
 #endif
