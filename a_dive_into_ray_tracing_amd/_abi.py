@@ -186,6 +186,22 @@ SIGNATURES = {
     "rt_nw_ctx_last_staging": (C.c_int, [C.c_void_p, _ip]),
     "rt_nw_debug_trace": (C.c_int, [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 3 + [C.c_uint64] + [C.c_int32] * 3 + [_fp, C.c_int32, _ip]),
     "rt_nw_debug_hits": (C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_uint64), C.c_int32, _ip, _fp, _ip]),
+    # progressive passes of the Next-Week renderer
+    "rt_nw_accum_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "rt_nw_render_pass": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 5 + [C.c_uint64] + [C.c_int32] * 3 + [C.c_void_p],
+    ),
+    "rt_nw_accum_resolve": (C.c_int, [C.c_void_p, C.c_void_p, _fp, C.c_void_p]),
+    "rt_nw_accum_export": (C.c_int, [C.c_void_p, _lp, C.c_size_t, _ip]),
+    "rt_nw_accum_import": (C.c_int, [C.c_void_p, _lp, C.c_size_t, C.c_int32]),
+    "rt_nw_accum_save": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 4 + [C.c_uint64]),
+    "rt_nw_accum_load": (
+        C.c_int,
+        [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 6 + [C.c_uint64, _ip],
+    ),
+    "rt_nw_accum_info": (C.c_int, [C.c_char_p, _ip, C.POINTER(C.c_uint64)]),
+    "rt_nw_scene_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -29,10 +29,13 @@ namespace nw {
 struct Args {
   Cam<float> cam;
   float time0, time1;
-  int32_t W, H, spp, max_depth;
+  int32_t W, H, s_end, max_depth;  // s_end: one past the launch's last sample, s_base + its sample count
   uint64_t seed;
   int32_t row0, row_step, nrows_valid;
   int32_t tiles_x, tiles, chunk, nch, n_items;
+  // first sample of the launch (a progressive pass, rt_nw_render_pass; 0 in a plain render): item c of a tile
+  // takes the samples s_base + c * chunk + [0, ns).  Wave-uniform: one scalar add per item.
+  int32_t s_base;
 };
 
 // Two kernel shapes, the same per-path arithmetic (bit-identical images):
@@ -216,8 +219,8 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
                                          unsigned long long (&acc)[3][64], unsigned long long *__restrict__ accum,
                                          float *__restrict__ out, unsigned &nseg, const float *cl) {
   const int tile = item / a.nch;
-  const int s0 = (item - tile * a.nch) * a.chunk;
-  const int ns = min(a.chunk, a.spp - s0);
+  const int s0 = a.s_base + (item - tile * a.nch) * a.chunk;
+  const int ns = min(a.chunk, a.s_end - s0);  // (the job decode below works on the item-local q < nv * ns)
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int x0 = tx * 8, y0 = ty * 8;
   const int vw = min(8, a.W - x0), vh = min(8, a.nrows_valid - y0);
@@ -234,7 +237,7 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
   // max_depth < 2^24 is checked on the host) in one register
   int pxd = 0;
   Xoro rng;
-  // job q -> pixel q % nv, sample s0 + q / nv; camera ray main.cu:139-141.
+  // job q -> pixel q % nv, sample s0 + q / nv (s0 includes the launch's s_base); camera ray main.cu:139-141.
   // Grid kernels: q / d = umulhi(2q, ceil(2^31 / d)), exact for d <= 64,
   // q < 2^25 (the RTIOW kernel's job decode, tests/test_kernel_arith.py;
   // chunk <= 65535 keeps q < 2^22) — a multiply instead of the 32-bit division
@@ -710,6 +713,11 @@ struct rt_nw_ctx {
   size_t accum_cap = 0;
   float *scratch = nullptr;
   size_t scratch_cap = 0;
+  // progressive passes (rt_nw_accum_reset / rt_nw_render_pass): an accumulator of its own, pass_W x pass_rows x 3
+  // fixed-point sums holding pass_spp samples; accum above stays the scratch of a single render
+  unsigned long long *pass_accum = nullptr;
+  size_t pass_cap = 0;
+  int32_t pass_W = 0, pass_rows = 0, pass_spp = 0;
   unsigned long long *segments = nullptr;
   unsigned *counter = nullptr;  // persistent kernel's work-item counter
   int32_t persist_blocks = 0;   // resident 16-wave blocks (CUs x blocks per CU), BVH kernels
@@ -843,7 +851,7 @@ RTMI_EXPORT int rt_nw_ctx_destroy(rt_nw_ctx *ctx) {
   for (void *p : {(void *)ctx->obj, (void *)ctx->obj_id, (void *)ctx->med, (void *)ctx->med_id, (void *)ctx->inst, (void *)ctx->mat, (void *)ctx->tex,
                   (void *)ctx->pvec, (void *)ctx->pperm, (void *)ctx->img, (void *)ctx->imgd, (void *)ctx->nodes,
                   (void *)ctx->accum, (void *)ctx->scratch, (void *)ctx->segments, (void *)ctx->counter,
-                  (void *)ctx->grid_cells, (void *)ctx->grid_refs, (void *)ctx->grid_big})
+                  (void *)ctx->grid_cells, (void *)ctx->grid_refs, (void *)ctx->grid_big, (void *)ctx->pass_accum})
     if (p) (void)hipFree(p);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
@@ -1145,17 +1153,31 @@ RTMI_EXPORT int rt_nw_ctx_accel_info(rt_nw_ctx *ctx, int32_t *accel, int32_t *di
   return RT_OK;
 }
 
-RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp,
-                                  int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
-                                  float *dev_strip, void *stream) {
-  if (!ctx || !cam || !dev_strip) return set_error(RT_EINVAL, "rt_nw_render_rows: null argument");
+namespace {
+// rt_nw_render_rows, and with pass_accum set a progressive pass (rt_nw_render_pass): samples s_base + [0, spp)
+// of the rows are added to that fixed-point accumulator ([nrows][W][3], zeroed by rt_nw_accum_reset) by the
+// CHUNKED instantiation of the same kernel shape; nothing is cleared, no float is written and dev_strip is
+// not read.  `who` names the entry point in error messages.
+int check_rows_args(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp, int32_t max_depth,
+                    int32_t row0, int32_t row_step, int32_t nrows, int32_t s_base, bool pass, const char *who) {
+  if (!ctx || !cam) return set_error(RT_EINVAL, "%s: null argument", who);
   if (ctx->nobj + ctx->nmed <= 0) return set_error(RT_EINVAL, "no scene uploaded (rt_nw_ctx_set_scene)");
-  if (W < 1 || H < 1 || spp < 1 || spp >= (1 << 24) || max_depth < 1 || max_depth >= (1 << 24) ||
+  if (W < 1 || H < 1 || spp < 1 || (!pass && spp >= (1 << 24)) || max_depth < 1 || max_depth >= (1 << 24) ||
       int64_t(W) * H >= (int64_t(1) << 40))
-    return set_error(RT_EINVAL, "rt_nw_render_rows: bad size (W, H, spp >= 1, spp < 2^24, 1 <= max_depth < 2^24)");
-  if (nrows < 1 || row_step < 1 || row0 < 0 || row0 >= H) return set_error(RT_EINVAL, "rt_nw_render_rows: bad row set");
+    return set_error(RT_EINVAL, "%s: bad size (W, H, spp >= 1, spp < 2^24, 1 <= max_depth < 2^24)", who);
+  if (nrows < 1 || row_step < 1 || row0 < 0 || row0 >= H) return set_error(RT_EINVAL, "%s: bad row set", who);
   if (!(cam->time0 >= 0.0 && cam->time1 <= 1.0 && cam->time0 <= cam->time1))
-    return set_error(RT_EINVAL, "rt_nw_render_rows: shutter must lie in [0, 1]");
+    return set_error(RT_EINVAL, "%s: shutter must lie in [0, 1]", who);
+  // a pass's samples keep inside the RNG key's 24 bits (checked by rt_nw_render_pass)
+  if (s_base < 0 || int64_t(s_base) + spp > (int64_t(1) << 24)) return set_error(RT_EINVAL, "%s: bad sample range", who);
+  return RT_OK;
+}
+
+int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp, int32_t max_depth,
+                     uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows, float *dev_strip, void *stream,
+                     int32_t s_base, unsigned long long *pass_accum, const char *who) {
+  if (int rc = check_rows_args(ctx, cam, W, H, spp, max_depth, row0, row_step, nrows, s_base, pass_accum != nullptr, who)) return rc;
+  if (!dev_strip && !pass_accum) return set_error(RT_EINVAL, "%s: null argument", who);
   const int32_t valid = std::min<int64_t>(nrows, (int64_t(H) - 1 - row0) / row_step + 1);
   Guard g(ctx->device);
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
@@ -1165,7 +1187,8 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   a.time1 = float(cam->time1);
   a.W = W;
   a.H = H;
-  a.spp = spp;
+  a.s_end = s_base + spp;
+  a.s_base = s_base;
   a.max_depth = max_depth;
   a.seed = seed;
   a.row0 = row0;
@@ -1199,7 +1222,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
     hipStream_t s;
     ~MarkDone() { (void)hipEventRecord(c->last_done, s); }
   } mark_done{ctx, st};
-  if (valid < nrows)  // rows past H: zero
+  if (valid < nrows && !pass_accum)  // rows past H: zero (a pass leaves them as rt_nw_accum_reset zeroed them)
     HIP_TRY(hipMemsetAsync(dev_strip + size_t(valid) * W * 3, 0, size_t(nrows - valid) * W * 3 * sizeof(float), st));
   HIP_TRY(hipMemsetAsync(ctx->segments, 0, sizeof(unsigned long long), st));
   const View v = view_of(ctx);
@@ -1290,33 +1313,35 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   ctx->last_kernel[3] = a.chunk;
   ctx->last_staging[0] = !use_grid && (persist || lds_nodes) ? 1 : 0;
   ctx->last_staging[1] = use_grid || (persist ? p_objs : lds_objs) ? 1 : 0;
+  // (a pass adds into its own accumulator; ctx->accum stays the per-render scratch, sized below)
+  unsigned long long *acc_buf = pass_accum;
   auto launch_t = [&](auto chunked, auto tri) {
     constexpr bool C = decltype(chunked)::value;
     constexpr int T = decltype(tri)::value;
     if constexpr (T < 3) {  // (a scene with placements has no grid)
       if (simple) {
-        hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+        hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
         return;
       }
       if (persist && use_grid) {
-        hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+        hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
         return;
       }
       if (!persist && g_grid) {
-        hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+        hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
         return;
       }
     }
     if (persist && p_objs)
-      hipLaunchKernelGGL((render_persistent<C, true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+      hipLaunchKernelGGL((render_persistent<C, true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
     else if (persist)
-      hipLaunchKernelGGL((render_persistent<C, false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments, ctx->counter);
+      hipLaunchKernelGGL((render_persistent<C, false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
     else if (lds_objs)
-      hipLaunchKernelGGL((render_kernel<C, true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
     else if (lds_nodes)
-      hipLaunchKernelGGL((render_kernel<C, true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
     else
-      hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ctx->accum, dev_strip, ctx->segments);
+      hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, acc_buf, dev_strip, ctx->segments);
   };
   auto launch = [&](auto chunked) {
     if (ctx->has_tri == 5) launch_t(chunked, Tri5{});
@@ -1326,7 +1351,9 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
     else if (ctx->has_tri) launch_t(chunked, Tri1{});
     else launch_t(chunked, Tri0{});
   };
-  if (a.nch > 1) {
+  if (pass_accum) {  // chunked whatever nch is: no memset, no finalize (rt_nw_accum_resolve)
+    launch(std::true_type{});
+  } else if (a.nch > 1) {
     const size_t nv = size_t(valid) * W * 3;
     if (nv > ctx->accum_cap) {
       HIP_TRY(hipStreamSynchronize(st));
@@ -1334,6 +1361,7 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
       ctx->accum_cap = nv;
     }
     HIP_TRY(hipMemsetAsync(ctx->accum, 0, nv * sizeof(unsigned long long), st));
+    acc_buf = ctx->accum;
     launch(std::true_type{});
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(finalize_kernel, dim3(unsigned((nv + 255) / 256)), dim3(256), 0, st, ctx->accum, dev_strip, nv);
@@ -1342,6 +1370,15 @@ RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32
   }
   HIP_TRY(hipGetLastError());
   return RT_OK;
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp,
+                                  int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
+                                  float *dev_strip, void *stream) {
+  if (!dev_strip) return set_error(RT_EINVAL, "rt_nw_render_rows: null argument");
+  return render_rows_impl(ctx, cam, W, H, spp, max_depth, seed, row0, row_step, nrows, dev_strip, stream, 0, nullptr,
+                          "rt_nw_render_rows");
 }
 
 RTMI_EXPORT int rt_nw_render(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp,
@@ -1358,6 +1395,153 @@ RTMI_EXPORT int rt_nw_render(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W,
   if (int rc = rt_nw_render_rows(ctx, cam, W, H, spp, max_depth, seed, 0, 1, H, ctx->scratch, ctx->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(sum, ctx->scratch, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// progressive passes (DESIGN.md §9 "Progressive passes"; as rtmi_device.hip's)
+// ---------------------------------------------------------------------------
+// The pass accumulator holds the fixed-point sums (2^-32, int64) of the passes
+// so far.  A sample's contribution depends on (seed, pixel, sample index) alone
+// and integer addition has no order, so any split of [0, spp) into passes gives
+// the sums of one rt_nw_render of spp samples, bit for bit.
+RTMI_EXPORT int rt_nw_accum_reset(rt_nw_ctx *ctx, int32_t W, int32_t nrows) {
+  if (!ctx) return set_error(RT_EINVAL, "null ctx");
+  if (W < 1 || nrows < 1 || int64_t(W) * nrows >= (int64_t(1) << 40))
+    return set_error(RT_EINVAL, "rt_nw_accum_reset: bad size %dx%d", W, nrows);
+  Guard g(ctx->device);
+  const size_t n = size_t(W) * size_t(nrows) * 3;
+  if (ctx->last_stream) HIP_TRY(hipStreamSynchronize(ctx->last_stream));  // no pass still adding
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (ctx->pass_cap < n) {
+    ctx->pass_cap = 0;
+    ctx->pass_W = ctx->pass_rows = ctx->pass_spp = 0;
+    if (int rc = alloc_copy<unsigned long long>(&ctx->pass_accum, nullptr, n)) return rc;
+    ctx->pass_cap = n;
+  }
+  ctx->pass_W = W;
+  ctx->pass_rows = nrows;
+  ctx->pass_spp = 0;
+  HIP_TRY(hipMemsetAsync(ctx->pass_accum, 0, n * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_render_pass(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t s_begin,
+                                  int32_t s_count, int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step,
+                                  int32_t nrows, void *stream) {
+  if (!ctx || !cam) return set_error(RT_EINVAL, "rt_nw_render_pass: null argument");
+  // (the RNG key gives a sample 24 bits; 2^24 samples of at most 64.0 stay below 2^62 in the accumulator)
+  if (s_begin < 0 || s_count < 0 || int64_t(s_begin) + s_count > (int64_t(1) << 24))
+    return set_error(RT_EINVAL, "rt_nw_render_pass: bad sample range [%d, +%d) (samples lie in [0, 2^24))", s_begin, s_count);
+  if (!ctx->pass_accum || !ctx->pass_W || W != ctx->pass_W || nrows != ctx->pass_rows)
+    return set_error(RT_EINVAL, "rt_nw_render_pass: accumulator is not %dx%d (call rt_nw_accum_reset)", W, nrows);
+  if (size_t(W) * size_t(nrows) * 3 > ctx->pass_cap) return set_error(RT_EHIP, "internal: pass accumulator too small");
+  if (s_count == 0)  // nothing to add: the arguments are still a render's
+    return check_rows_args(ctx, cam, W, H, 1, max_depth, row0, row_step, nrows, s_begin == (1 << 24) ? 0 : s_begin, true, "rt_nw_render_pass");
+  if (int rc = render_rows_impl(ctx, cam, W, H, s_count, max_depth, seed, row0, row_step, nrows, nullptr, stream, s_begin,
+                                ctx->pass_accum, "rt_nw_render_pass"))
+    return rc;
+  ctx->pass_spp += s_count;
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_accum_resolve(rt_nw_ctx *ctx, float *dev_sum, float *host_sum, void *stream) {
+  if (!ctx) return set_error(RT_EINVAL, "null ctx");
+  if (!ctx->pass_accum || !ctx->pass_W) return set_error(RT_EINVAL, "rt_nw_accum_resolve: no accumulator (rt_nw_accum_reset)");
+  if (!dev_sum && !host_sum) return set_error(RT_EINVAL, "rt_nw_accum_resolve: no output");
+  Guard g(ctx->device);
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const size_t n = size_t(ctx->pass_W) * size_t(ctx->pass_rows) * 3;
+  float *out = dev_sum;
+  if (!out) {  // through the context's float scratch, which renders share
+    if (n > ctx->scratch_cap) {
+      if (ctx->last_stream) HIP_TRY(hipStreamSynchronize(ctx->last_stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      ctx->scratch_cap = 0;
+      if (int rc = alloc_copy<float>(&ctx->scratch, nullptr, n)) return rc;
+      ctx->scratch_cap = n;
+    }
+    out = ctx->scratch;
+  }
+  // a resolve on another stream waits for the last pass (and, as it may write the shared scratch, it is
+  // itself work the next render waits for)
+  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
+  ctx->last_stream = st;
+  hipLaunchKernelGGL(finalize_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, ctx->pass_accum, out, n);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && host_sum) e = hipMemcpyAsync(host_sum, out, n * sizeof(float), hipMemcpyDeviceToHost, st);
+  (void)hipEventRecord(ctx->last_done, st);
+  if (e == hipSuccess && host_sum) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_accum_resolve: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+// Checkpoint / resume: the raw fixed-point accumulator (W * nrows * 3 int64) and the number of samples it holds.
+RTMI_EXPORT int rt_nw_accum_export(rt_nw_ctx *ctx, int64_t *host, size_t n, int32_t *spp_done) {
+  if (!ctx || !host) return set_error(RT_EINVAL, "rt_nw_accum_export: null argument");
+  const size_t want = size_t(ctx->pass_W) * size_t(ctx->pass_rows) * 3;
+  if (!ctx->pass_accum || !want || n != want)
+    return set_error(RT_EINVAL, "rt_nw_accum_export: size %zu, accumulator %zu (rt_nw_accum_reset)", n, want);
+  Guard g(ctx->device);
+  HIP_TRY(hipStreamSynchronize(ctx->last_stream ? ctx->last_stream : ctx->stream));
+  HIP_TRY(hipMemcpy(host, ctx->pass_accum, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (spp_done) *spp_done = ctx->pass_spp;
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_accum_import(rt_nw_ctx *ctx, const int64_t *host, size_t n, int32_t spp_done) {
+  if (!ctx || !host) return set_error(RT_EINVAL, "rt_nw_accum_import: null argument");
+  const size_t want = size_t(ctx->pass_W) * size_t(ctx->pass_rows) * 3;
+  if (!ctx->pass_accum || !want || n != want)
+    return set_error(RT_EINVAL, "rt_nw_accum_import: size %zu, accumulator %zu (call rt_nw_accum_reset)", n, want);
+  if (spp_done < 0 || spp_done > (1 << 24)) return set_error(RT_EINVAL, "rt_nw_accum_import: sample count outside [0, 2^24]");
+  Guard g(ctx->device);
+  if (ctx->last_stream) HIP_TRY(hipStreamSynchronize(ctx->last_stream));
+  HIP_TRY(hipMemcpy(ctx->pass_accum, host, n * sizeof(int64_t), hipMemcpyHostToDevice));
+  ctx->pass_spp = spp_done;
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_accum_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t H,
+                                 int32_t row0, int32_t row_step, int32_t max_depth, uint64_t seed) {
+  if (!ctx || !path || !scene || !cam) return set_error(RT_EINVAL, "rt_nw_accum_save: null argument");
+  if (!ctx->pass_accum || !ctx->pass_W) return set_error(RT_EINVAL, "rt_nw_accum_save: no accumulator (rt_nw_accum_reset)");
+  CkptHeader h{};
+  if (int rc = rt_nw_scene_hash(scene, &h.scene_hash)) return rc;
+  const size_t n = size_t(ctx->pass_W) * size_t(ctx->pass_rows) * 3;
+  std::vector<int64_t> raw(n);
+  if (int rc = rt_nw_accum_export(ctx, raw.data(), n, &h.spp_done)) return rc;
+  h.W = ctx->pass_W;
+  h.H = H;
+  h.row0 = row0;
+  h.row_step = row_step;
+  h.nrows = ctx->pass_rows;
+  h.max_depth = max_depth;
+  h.seed = seed;
+  h.camera_hash = camera_hash(cam);
+  return ckpt_write(path, h, raw.data());
+}
+
+RTMI_EXPORT int rt_nw_accum_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W,
+                                 int32_t H, int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed,
+                                 int32_t *spp_done) {
+  if (!ctx || !path || !scene || !cam || !spp_done) return set_error(RT_EINVAL, "rt_nw_accum_load: null argument");
+  if (W < 1 || nrows < 1) return set_error(RT_EINVAL, "rt_nw_accum_load: bad size %dx%d", W, nrows);
+  uint64_t sh = 0;
+  if (int rc = rt_nw_scene_hash(scene, &sh)) return rc;
+  CkptHeader h{};
+  if (int rc = ckpt_read(path, h, nullptr)) return rc;
+  if (h.W != W || h.H != H || h.row0 != row0 || h.row_step != row_step || h.nrows != nrows || h.max_depth != max_depth ||
+      h.seed != seed || h.scene_hash != sh || h.camera_hash != camera_hash(cam))
+    return set_error(RT_EINVAL, "rt_nw_accum_load: %s was made for another render (size, rows, depth, seed, scene or camera)",
+                     path);
+  if (h.spp_done < 0 || h.spp_done > (1 << 24)) return set_error(RT_EIO, "rt_nw_accum_load: %s holds a bad sample count", path);
+  std::vector<int64_t> raw;
+  if (int rc = ckpt_read(path, h, &raw)) return rc;  // (the header now matches this render: the body is W * nrows * 3)
+  if (int rc = rt_nw_accum_reset(ctx, W, nrows)) return rc;
+  if (int rc = rt_nw_accum_import(ctx, raw.data(), raw.size(), h.spp_done)) return rc;
+  *spp_done = h.spp_done;
   return RT_OK;
 }
 

@@ -9,7 +9,18 @@
 //                  [--out FILE|-] [--p6] [--rtl]
 //   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
 //                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble] [--width W] ...
-//   either form: [--shutter T0,T1]
+//   either form: [--shutter T0,T1] [--pass-spp N] [--checkpoint FILE] [--time-limit SECONDS] [--pfm FILE]
+//
+// --pass-spp N renders in passes of N samples (rt_nw_render_pass), each a
+// bounded kernel launch; the image is bit for bit the one of a single render of
+// --spp samples.  --checkpoint FILE saves the accumulator after every pass
+// (rt_nw_accum_save) and resumes from the file when it exists: a second run
+// with a larger --spp continues where the first ended.  --time-limit SECONDS
+// starts no new pass once that much time has passed since the first one began
+// (at least one pass always runs); the run then saves, writes the image of the
+// samples it has, reports their count and exits 0.  --checkpoint or
+// --time-limit without --pass-spp: passes of kDefaultPassSpp.  stderr carries
+// {"pass_done_spp": n} per pass.  --pfm FILE writes the mean image (floats).
 //
 // --obj (exclusive with --scene) renders a Wavefront OBJ mesh
 // (rt_nw_scene_obj_stage): scaled and centred into the box [-1, 1] x [0, 2] x
@@ -33,6 +44,7 @@
 // PIL).  The P3 output follows main.cu:563-575: int(255.99 * sqrt(mean)) per
 // channel, top row first, NOT clamped (lights print values above 255, as the
 // reference does); --p6 clamps to bytes.  Timing goes to stderr as JSON.
+#include <algorithm>
 #include <cctype>
 #include <chrono>
 #include <cmath>
@@ -43,6 +55,12 @@
 #include <vector>
 
 #include "../../include/rtmi_nw.h"
+
+// Default --pass-spp.  Measured at 800 x 800 x 1024 against one rt_nw_render (profiles/progressive/README.md): the
+// final scene in passes of 1024 / 256 / 64 / 16 samples costs -0.2 / +14 / +42 / +175 %, a 4 x 4 field of a
+// 5 120-triangle mesh -0.1 / +5.5 / +25 / +121 % — a small pass gives the persistent kernels few, short work
+// items.  1024 is free and still a pass of about a second on those scenes.
+static const int kDefaultPassSpp = 1024;
 
 static int die(const char *what, int rc) {
   std::fprintf(stderr, "rtmi_nw_render: %s failed (%d): %s\n", what, rc, rt_last_error());
@@ -80,7 +98,9 @@ static bool read_p6(const char *path, std::vector<uint8_t> &px, int &w, int &h) 
 }
 
 int main(int argc, char **argv) {
-  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture;
+  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture, checkpoint, pfm;
+  int pass_spp = 0;
+  double time_limit = -1;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
   bool copies_given = false, move_given = false, shutter_given = false, tumble = false;
@@ -128,6 +148,12 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--out")) out = need("--out");
     else if (!std::strcmp(argv[a], "--p6")) p6 = 1;
     else if (!std::strcmp(argv[a], "--rtl")) rtl = 1;
+    else if (!std::strcmp(argv[a], "--pass-spp")) pass_spp = std::atoi(need("--pass-spp"));
+    else if (!std::strcmp(argv[a], "--checkpoint")) checkpoint = need("--checkpoint");
+    else if (!std::strcmp(argv[a], "--pfm")) pfm = need("--pfm");
+    else if (!std::strcmp(argv[a], "--time-limit")) {
+      if (!numbers(need("--time-limit"), &time_limit, 1) || time_limit < 0) { std::fprintf(stderr, "--time-limit takes SECONDS >= 0\n"); return 2; }
+    }
     else {
       std::fprintf(stderr, "usage: %s [--scene 1..8|name] [--width W] [--height H] [--spp S] [--depth D]\n"
                            "          [--seed N] [--texture FILE.ppm] [--out FILE|-] [--p6] [--rtl]\n"
@@ -135,6 +161,14 @@ int main(int argc, char **argv) {
                            "          [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble]\n"
                            "          [--width W] [--height H] ...\n"
                            "       either form: [--shutter T0,T1] (the camera's shutter, 0 <= T0 <= T1 <= 1; default 0,1)\n"
+                           "                    [--pass-spp N] [--checkpoint FILE] [--time-limit SECONDS] [--pfm FILE]\n"
+                           "  --pass-spp N: render in passes of N samples, the same image bit for bit; --checkpoint FILE: save\n"
+                           "         after every pass and resume from FILE when it exists (a larger --spp continues a run);\n"
+                           "         --time-limit SECONDS: start no new pass after that long (one always runs), then save, write\n"
+                           "         the image of the samples so far and exit 0.  Without --pass-spp the last two use passes of\n"
+                           "         %d samples.  Measured cost of splitting 1024 spp at 800 x 800 into passes of 1024 / 256 / 64 /\n"
+                           "         16 samples: final scene -0.2 / +14 / +42 / +175 %%, a 4 x 4 mesh field -0.1 / +5.5 / +25 / +121 %%\n"
+                           "  --pfm FILE: the mean image as floats\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
                            "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
@@ -146,7 +180,7 @@ int main(int argc, char **argv) {
                            "         times [0, 1] (motion blur under the default shutter)\n"
                            "  --obj-tumble (needs --obj): every copy as an affine placement of the shared mesh, scaled by\n"
                            "         0.75 + 0.25 sin(2.9 q), turned 37 q degrees about a skew axis and stood on the ground\n",
-                   argv[0], argv[0]);
+                   argv[0], argv[0], kDefaultPassSpp);
       return 2;
     }
   }
@@ -177,6 +211,9 @@ int main(int argc, char **argv) {
   if (obj.empty() && (which < 1 || which > 8)) { std::fprintf(stderr, "unknown scene %s\n", scene.c_str()); return 2; }
   if (!obj.empty()) which = 0;
   if (H < 0) H = W;  // aspect_ratio = 1.0, main.cu:517-519
+  if (pass_spp < 0) { std::fprintf(stderr, "--pass-spp takes a count >= 1\n"); return 2; }
+  if (pass_spp == 0 && (!checkpoint.empty() || time_limit >= 0)) pass_spp = kDefaultPassSpp;
+  if (pass_spp > 0 && spp < 1) { std::fprintf(stderr, "--spp takes a count >= 1\n"); return 2; }
   std::vector<uint8_t> img;
   int iw = 0, ih = 0;
   if (!texture.empty() && !read_p6(texture.c_str(), img, iw, ih)) {
@@ -229,14 +266,44 @@ int main(int argc, char **argv) {
   if ((rc = rt_nw_ctx_set_scene(ctx, s))) return die("rt_nw_ctx_set_scene", rc);
   std::vector<float> sum(size_t(W) * H * 3);
   const auto t0 = std::chrono::steady_clock::now();
-  if ((rc = rt_nw_render(ctx, &cam, W, H, spp, depth, seed, sum.data()))) return die("rt_nw_render", rc);
-  const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   uint64_t segs = 0;
-  rt_nw_ctx_last_segments(ctx, &segs);
+  int spp_resumed = 0;
+  if (pass_spp > 0) {
+    if ((rc = rt_nw_accum_reset(ctx, W, H))) return die("rt_nw_accum_reset", rc);
+    int done = 0;
+    if (!checkpoint.empty()) {
+      if (FILE *probe = std::fopen(checkpoint.c_str(), "rb")) {
+        std::fclose(probe);
+        if ((rc = rt_nw_accum_load(ctx, checkpoint.c_str(), s, &cam, W, H, 0, 1, H, depth, seed, &done))) return die("rt_nw_accum_load", rc);
+        spp_resumed = done;
+      }
+    }
+    bool first = true;
+    while (done < spp) {
+      const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (!first && time_limit >= 0 && elapsed >= time_limit) break;
+      first = false;
+      const int k = std::min(pass_spp, spp - done);
+      if ((rc = rt_nw_render_pass(ctx, &cam, W, H, done, k, depth, seed, 0, 1, H, nullptr))) return die("rt_nw_render_pass", rc);
+      done += k;
+      uint64_t ps = 0;  // (waits for the pass)
+      if ((rc = rt_nw_ctx_last_segments(ctx, &ps))) return die("rt_nw_ctx_last_segments", rc);
+      segs += ps;
+      if (!checkpoint.empty() && (rc = rt_nw_accum_save(ctx, checkpoint.c_str(), s, &cam, H, 0, 1, depth, seed))) return die("rt_nw_accum_save", rc);
+      std::fprintf(stderr, "{\"pass_done_spp\": %d}\n", done);
+    }
+    if ((rc = rt_nw_accum_resolve(ctx, nullptr, sum.data(), nullptr))) return die("rt_nw_accum_resolve", rc);
+    spp = done;  // (under --time-limit: the samples the image holds)
+  } else {
+    if ((rc = rt_nw_render(ctx, &cam, W, H, spp, depth, seed, sum.data()))) return die("rt_nw_render", rc);
+    rt_nw_ctx_last_segments(ctx, &segs);
+  }
+  const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const double rendered = double(W) * H * std::max(spp - spp_resumed, 0);
   std::fprintf(stderr,
                "{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"seconds\": %.6f, "
                "\"msamples_per_s\": %.3f, \"segments_per_sample\": %.4f}\n",
-               which, W, H, spp, depth, seconds, double(W) * H * spp / seconds / 1e6, double(segs) / (double(W) * H * spp));
+               which, W, H, spp, depth, seconds, rendered / seconds / 1e6, rendered > 0 ? double(segs) / rendered : 0.0);
   rt_nw_ctx_destroy(ctx);
   rt_nw_scene_destroy(s);
 
@@ -257,5 +324,6 @@ int main(int argc, char **argv) {
       }
     }
   if (f != stdout) std::fclose(f);
+  if (!pfm.empty() && (rc = rt_write_pfm(pfm.c_str(), sum.data(), W, H, spp))) return die("rt_write_pfm", rc);
   return 0;
 }

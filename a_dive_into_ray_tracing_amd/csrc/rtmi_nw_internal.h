@@ -84,5 +84,24 @@ int scene_instancing_stats(rt_nw_scene *s, int32_t out[6]);
 // rt_nw_scene_grid_stats: the grid of build_device_scene, host only.
 int scene_grid_stats(rt_nw_scene *s, int32_t *dims3, int32_t *max_cell, int32_t *n_big, int32_t *n_refs);
 
+// Checkpoint file of the progressive accumulator (rt_nw_accum_save / _load / _info; rtmi_nw.h): this
+// header, little-endian, then the int64 sums [nrows][W][3].  The layout of the One-Weekend file
+// (rtmi_device.hip) under a magic of its own.  Host only (rtmi_nw_scene.cpp).
+struct CkptHeader {
+  char magic[8];  // "RTMINWA1"
+  int32_t W, H, row0, row_step, nrows, spp_done, max_depth, zero;
+  uint64_t seed, scene_hash, camera_hash;
+};
+static_assert(sizeof(CkptHeader) == 64, "checkpoint header layout");
+// Writes path atomically (path + ".tmp", then rename): the header with the magic filled in, then the
+// W * nrows * 3 sums of raw.  RT_EIO.
+int ckpt_write(const char *path, const CkptHeader &h, const int64_t *raw);
+// The header of path: RT_EIO for a file that cannot be opened, is shorter than a header or starts with
+// another magic.  With raw: also the body, the header's W * nrows * 3 sums — RT_EIO when W < 1 or nrows <
+// 0, or when the file holds fewer or more bytes than that.
+int ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *raw);
+// FNV-1a 64 of the camera's bytes (the shutter included)
+uint64_t camera_hash(const rt_nw_camera *cam);
+
 }  // namespace nw
 }  // namespace rtmi

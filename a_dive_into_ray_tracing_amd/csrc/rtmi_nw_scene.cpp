@@ -2030,6 +2030,145 @@ RTMI_EXPORT int rt_nw_scene_flat_attr(rt_nw_scene *s, int32_t *n_attr, const flo
   return RT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// scene hash and checkpoint files of the progressive accumulator (rtmi_nw.h)
+// ---------------------------------------------------------------------------
+namespace {
+constexpr uint64_t kFnvBasis = 14695981039346656037ull, kFnvPrime = 1099511628211ull;
+struct Fnv {
+  uint64_t h = kFnvBasis;
+  void bytes(const void *p, size_t n) {
+    const unsigned char *b = static_cast<const unsigned char *>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * kFnvPrime;
+  }
+  void i64(int64_t v) { bytes(&v, sizeof v); }
+  template <class T> void table(const std::vector<T> &v) {  // count, then the records' bytes
+    i64(int64_t(v.size()));
+    if (!v.empty()) bytes(v.data(), v.size() * sizeof(T));
+  }
+};
+constexpr char kCkptMagic[8] = {'R', 'T', 'M', 'I', 'N', 'W', 'A', '1'};
+}  // namespace
+
+// The serialisation is written out beside the declaration (rtmi_nw.h).  Every
+// record type below is made of 4-byte fields without padding, and the builder
+// zero-fills the words it does not use.
+RTMI_EXPORT int rt_nw_scene_hash(rt_nw_scene *s, uint64_t *out) {
+  if (!s || !out) return set_error(RT_EINVAL, "rt_nw_scene_hash: null argument");
+  // the flat view at time 0; a caller's view at another time is put back
+  const bool had = s->flat_valid;
+  const float t_had = s->flat_time, t0 = 0.f;
+  if (int rc = flatten(s, &t0)) return rc;
+  Fnv f;
+  f.bytes("RTMINWS1", 8);
+  f.table(s->flat_obj);
+  f.table(s->flat_inst);
+  f.table(s->mat);
+  f.table(s->tex);
+  f.table(s->perlin_vec);
+  f.table(s->perlin_perm);
+  f.table(s->image);
+  f.table(s->image_px);
+  f.bytes(s->background, sizeof s->background);
+  f.table(s->attr);
+  f.table(s->flat_attr);
+  f.i64(int64_t(s->flat_place.size()));
+  for (const rt_nw_scene::Place &p : s->flat_place) {
+    const int32_t w[3] = {p.first, p.count, (p.x.moving ? 1 : 0) | (p.x.affine ? 2 : 0)};
+    f.bytes(w, sizeof w);
+    if (p.x.moving) {  // what the kernels form off(T) from (build_device_scene)
+      float o[6];
+      motion_ends(p.x, o, o + 3);
+      const float t[2] = {float(p.x.time0), float(p.x.time1)};
+      f.bytes(o, sizeof o);
+      f.bytes(t, sizeof t);
+    }
+    if (p.x.affine) {  // the placement's AffInst rows: M = float(A^-1), off = float(b)
+      double inv[9];
+      (void)affine_inverse(p.x.A, inv);  // (checked when the world was flattened)
+      float m[12];
+      for (int i = 0; i < 9; ++i) m[i] = float(inv[i]);
+      for (int a = 0; a < 3; ++a) m[9 + a] = float(p.x.t[a]);
+      f.bytes(m, sizeof m);
+    }
+  }
+  *out = f.h;
+  if (had && s->n_moves > 0 && std::memcmp(&t_had, &t0, sizeof(float)) != 0) return flatten(s, &t_had);
+  return RT_OK;
+}
+
+namespace rtmi {
+namespace nw {
+
+uint64_t camera_hash(const rt_nw_camera *cam) {
+  static_assert(sizeof(rt_nw_camera) % sizeof(double) == 0, "rt_nw_camera is doubles only: no padding to hash");
+  Fnv f;
+  f.bytes(cam, sizeof *cam);
+  return f.h;
+}
+
+int ckpt_write(const char *path, const CkptHeader &h_in, const int64_t *raw) {
+  if (!path || !raw || h_in.W < 1 || h_in.nrows < 0) return set_error(RT_EINVAL, "rt_nw_accum_save: bad argument");
+  CkptHeader h = h_in;
+  std::memcpy(h.magic, kCkptMagic, 8);
+  h.zero = 0;
+  const size_t n = size_t(h.W) * size_t(h.nrows) * 3;
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE *fp = std::fopen(tmp.c_str(), "wb");
+  if (!fp) return set_error(RT_EIO, "rt_nw_accum_save: cannot open %s", tmp.c_str());
+  bool ok = std::fwrite(&h, sizeof h, 1, fp) == 1 && (n == 0 || std::fwrite(raw, sizeof(int64_t), n, fp) == n);
+  if (std::fclose(fp) != 0) ok = false;
+  if (!ok || std::rename(tmp.c_str(), path) != 0) {
+    std::remove(tmp.c_str());
+    return set_error(RT_EIO, "rt_nw_accum_save: write to %s failed", path);
+  }
+  return RT_OK;
+}
+
+int ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *raw) {
+  if (!path) return set_error(RT_EINVAL, "null path");
+  FILE *fp = std::fopen(path, "rb");
+  if (!fp) return set_error(RT_EIO, "cannot open %s", path);
+  CkptHeader r{};
+  if (std::fread(&r, sizeof r, 1, fp) != 1 || std::memcmp(r.magic, kCkptMagic, 8) != 0) {
+    std::fclose(fp);
+    return set_error(RT_EIO, "%s is not a Next-Week checkpoint", path);
+  }
+  h = r;
+  if (!raw) {
+    std::fclose(fp);
+    return RT_OK;
+  }
+  // the body's size comes from the header: bounded before anything is allocated
+  const bool sane = r.W >= 1 && r.nrows >= 0 && int64_t(r.W) * r.nrows < (int64_t(1) << 40);
+  bool ok = sane && std::fseek(fp, 0, SEEK_END) == 0;
+  const long end = ok ? std::ftell(fp) : -1;
+  const uint64_t n = sane ? uint64_t(r.W) * uint64_t(r.nrows) * 3 : 0;
+  ok = ok && end >= 0 && uint64_t(end) == sizeof r + n * sizeof(int64_t) && std::fseek(fp, long(sizeof r), SEEK_SET) == 0;
+  if (ok) {
+    raw->resize(size_t(n));
+    ok = n == 0 || std::fread(raw->data(), sizeof(int64_t), size_t(n), fp) == size_t(n);
+  }
+  std::fclose(fp);
+  if (!ok) return set_error(RT_EIO, "%s is truncated, or holds more than its header states", path);
+  return RT_OK;
+}
+
+}  // namespace nw
+}  // namespace rtmi
+
+RTMI_EXPORT int rt_nw_accum_info(const char *path, int32_t out8[8], uint64_t out3[3]) {
+  if (!path || !out8 || !out3) return set_error(RT_EINVAL, "rt_nw_accum_info: null argument");
+  CkptHeader h{};
+  if (int rc = ckpt_read(path, h, nullptr)) return rc;
+  const int32_t v[8] = {h.W, h.H, h.row0, h.row_step, h.nrows, h.spp_done, h.max_depth, h.zero};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  out3[0] = h.seed;
+  out3[1] = h.scene_hash;
+  out3[2] = h.camera_hash;
+  return RT_OK;
+}
+
 RTMI_EXPORT int rt_nw_xorwow_uniforms(uint64_t seed, int32_t n, float *out) {
   if (n < 0 || (n > 0 && !out)) return set_error(RT_EINVAL, "rt_nw_xorwow_uniforms: bad argument");
   Xorwow g(seed);

@@ -20,7 +20,7 @@ import numpy as np
 
 from ._abi import RtNwCamera, RtNwFlat, check, load
 
-__all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "SCENES"]
+__all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "accum_info", "SCENES"]
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -254,6 +254,14 @@ class Scene:
             "n_obj": f.n_obj,
         }
 
+    def hash(self):
+        """FNV-1a 64 over everything of the scene that can change a pixel (host
+        only, rt_nw_scene_hash): what a checkpoint is tied to.  Equal in any two
+        processes that build the scene with the same calls."""
+        v = C.c_uint64()
+        check(load().rt_nw_scene_hash(self._h, C.byref(v)), "rt_nw_scene_hash")
+        return v.value
+
     def grid_stats(self):
         """The uniform grid a device context would build (host only,
         rt_nw_scene_grid_stats): {"dims", "max_cell", "n_big", "n_refs"}."""
@@ -388,6 +396,15 @@ def xorwow_uniforms(n, seed=1984):
     return out
 
 
+def accum_info(path):
+    """The header of a Next-Week checkpoint file (host only, rt_nw_accum_info)."""
+    v, u = (C.c_int32 * 8)(), (C.c_uint64 * 3)()
+    check(load().rt_nw_accum_info(str(path).encode(), v, u), "rt_nw_accum_info")
+    d = dict(zip(("W", "H", "row0", "row_step", "nrows", "spp_done", "max_depth", "zero"), list(v)))
+    d.update(zip(("seed", "scene_hash", "camera_hash"), list(u)))
+    return d
+
+
 def load_image(path):
     """Decode an image file (the earth texture) to h x w x 3 uint8, row 0 at the top (PIL)."""
     from PIL import Image
@@ -405,6 +422,7 @@ class NwRenderer:
 
     def set_scene(self, scene):
         check(load().rt_nw_ctx_set_scene(self._h, scene._h), "rt_nw_ctx_set_scene")
+        self._scene = scene  # (checkpoints carry its hash)
 
     def info(self):
         a, b = C.c_int32(), C.c_int32()
@@ -437,6 +455,72 @@ class NwRenderer:
     def render_rows(self, cam, W, H, spp, max_depth, seed, row0, row_step, nrows, dev_ptr, stream=0):
         check(load().rt_nw_render_rows(self._h, C.byref(cam), W, H, spp, max_depth, seed, row0, row_step, nrows,
                                        C.c_void_p(dev_ptr), C.c_void_p(stream)), "rt_nw_render_rows")
+
+    # ---- progressive passes (rt_nw_accum_* / rt_nw_render_pass) -----------
+    def accum_reset(self, W, nrows):
+        """A zeroed accumulator for a W x nrows strip (whole image: nrows = H)."""
+        check(load().rt_nw_accum_reset(self._h, W, nrows), "rt_nw_accum_reset")
+        self._acc_shape = (nrows, W, 3)
+
+    def render_pass(self, cam, W, H, s_begin, s_count, max_depth=50, seed=1984, row0=0, row_step=1, nrows=None, stream=0):
+        """Add samples [s_begin, s_begin + s_count) of the rows to the accumulator (async)."""
+        nrows = H if nrows is None else nrows
+        check(load().rt_nw_render_pass(self._h, C.byref(cam), W, H, s_begin, s_count, max_depth, seed, row0, row_step,
+                                       nrows, C.c_void_p(stream)), "rt_nw_render_pass")
+
+    def resolve(self, dev_ptr=None, stream=0):
+        """The accumulator as float sums: into the device strip dev_ptr
+        (asynchronous on `stream`), else returned as a host array [nrows, W, 3].
+        The accumulator is unchanged, so more passes may follow."""
+        if dev_ptr is not None:
+            check(load().rt_nw_accum_resolve(self._h, C.c_void_p(dev_ptr), None, C.c_void_p(stream)), "rt_nw_accum_resolve")
+            return None
+        out = np.zeros(getattr(self, "_acc_shape", (0, 0, 3)), np.float32)
+        check(load().rt_nw_accum_resolve(self._h, None, out.ctypes.data_as(_fp), C.c_void_p(stream)), "rt_nw_accum_resolve")
+        return out
+
+    def accum_export(self):
+        """(raw int64 fixed-point sums [nrows, W, 3], samples accumulated)."""
+        raw = np.zeros(getattr(self, "_acc_shape", (0, 0, 3)), np.int64)
+        done = C.c_int32()
+        check(load().rt_nw_accum_export(self._h, raw.ctypes.data_as(C.POINTER(C.c_int64)), raw.size, C.byref(done)),
+              "rt_nw_accum_export")
+        return raw, done.value
+
+    def accum_import(self, raw, spp_done):
+        raw = np.ascontiguousarray(raw, np.int64)
+        check(load().rt_nw_accum_import(self._h, raw.ctypes.data_as(C.POINTER(C.c_int64)), raw.size, spp_done),
+              "rt_nw_accum_import")
+
+    def progressive(self, cam, W, H, spp, pass_spp, max_depth=50, seed=1984, checkpoint=None, on_pass=None,
+                    row0=0, row_step=1, nrows=None):
+        """Samples [0, spp) in passes of pass_spp (each a bounded kernel), resuming
+        from `checkpoint` when that file exists and saving to it after every pass;
+        on_pass(done) is called after each.  Returns the float sums [nrows, W, 3]:
+        bit-identical to render(spp) for any pass split (as Renderer.progressive)."""
+        import os
+
+        if pass_spp < 1:
+            raise ValueError("pass_spp must be at least 1")
+        nrows = H if nrows is None else nrows
+        self.accum_reset(W, nrows)
+        L, sc = load(), self._scene._h
+        done = 0
+        if checkpoint and os.path.exists(checkpoint):
+            n = C.c_int32()
+            check(L.rt_nw_accum_load(self._h, str(checkpoint).encode(), sc, C.byref(cam), W, H, row0, row_step, nrows,
+                                     max_depth, seed, C.byref(n)), "rt_nw_accum_load")
+            done = n.value
+        while done < spp:
+            k = min(pass_spp, spp - done)
+            self.render_pass(cam, W, H, done, k, max_depth, seed, row0, row_step, nrows)
+            done += k
+            if checkpoint:  # (waits for the pass)
+                check(L.rt_nw_accum_save(self._h, str(checkpoint).encode(), sc, C.byref(cam), H, row0, row_step, max_depth,
+                                         seed), "rt_nw_accum_save")
+            if on_pass is not None:
+                on_pass(done)
+        return self.resolve()
 
     def debug_trace(self, cam, W, H, i, j, s, max_depth=50, seed=1984, cap=64, with_time=False):
         """The segments of one camera sample: rows (o.xyz, d.xyz, t, n.xyz) and (winner index, box face);

@@ -358,6 +358,72 @@ int rt_nw_render(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, 
 int rt_nw_render_rows(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp,
                       int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
                       float *dev_strip, void *stream);
+/* Progressive accumulation (resumable; as rtmi.h's rt_accum_*).  The context
+ * keeps a fixed-point accumulator for a W x nrows strip (the rows of
+ * rt_nw_render_rows' row set; nrows = H, row0 0, row_step 1 for a whole image),
+ * an allocation of its own that a plain rt_nw_render / rt_nw_render_rows in
+ * between does not touch.  rt_nw_render_pass adds samples [s_begin, s_begin +
+ * s_count) of every pixel, asynchronously on `stream`, with the kernel shape
+ * rt_nw_render_rows would choose; any split of [0, S) into passes, in any
+ * order, gives bit for bit the sums of one rt_nw_render(..., spp = S, ...) on
+ * the same rows, under any kernel shape, accelerator or RTMI_NW_CHUNK.
+ * rt_nw_ctx_last_segments after a pass is that pass's count; the counts of a
+ * split add up to the single render's.
+ * rt_nw_render_pass validates as rt_nw_render_rows does and also refuses
+ * (RT_EINVAL) s_begin < 0, s_count < 0, s_begin + s_count > 2^24 (the RNG key
+ * gives a sample 24 bits, and the accumulator holds 2^24 samples of at most
+ * 64.0 without overflow) and an accumulator of another W x nrows
+ * (rt_nw_accum_reset).  s_count == 0 succeeds and does nothing.  Rows past H
+ * stay zero.
+ * rt_nw_accum_resolve converts the sums to floats into a DEVICE strip and/or a
+ * HOST buffer (W*nrows*3; with a host buffer it waits); on another stream it
+ * first waits for the last pass.  The accumulator is unchanged: more passes
+ * may follow.  rt_nw_accum_export / rt_nw_accum_import copy the raw int64
+ * accumulator (n = W*nrows*3) and its sample count out / in. */
+int rt_nw_accum_reset(rt_nw_ctx *ctx, int32_t W, int32_t nrows);
+int rt_nw_render_pass(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t s_begin, int32_t s_count,
+                      int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows, void *stream);
+int rt_nw_accum_resolve(rt_nw_ctx *ctx, float *dev_sum, float *host_sum, void *stream);
+int rt_nw_accum_export(rt_nw_ctx *ctx, int64_t *host, size_t n, int32_t *spp_done);
+int rt_nw_accum_import(rt_nw_ctx *ctx, const int64_t *host, size_t n, int32_t spp_done);
+/* Checkpoint files: the accumulator plus what it was rendered from.  Little
+ * endian: a 64-byte header — the magic "RTMINWA1" (its digit is the version of
+ * the scene serialisation below); int32 W, H, row0, row_step, nrows, spp_done,
+ * max_depth, 0; uint64 seed, rt_nw_scene_hash of the scene, FNV-1a 64 of the
+ * rt_nw_camera's bytes (the shutter included) — then the int64 sums
+ * [nrows][W][3].  rt_nw_accum_save writes atomically (path + ".tmp", then
+ * rename).  rt_nw_accum_load resets the accumulator to W x nrows, fills it and
+ * sets *spp_done; RT_EINVAL ("made for another render") when size, rows,
+ * depth, seed, scene hash or camera hash differ; RT_EIO for a file that is
+ * missing, truncated, longer than its header states or of another magic (a
+ * One-Weekend checkpoint among them).  rt_nw_accum_info (host only) reads the
+ * header alone: out8 = the eight int32 in file order, out3 = {seed, scene
+ * hash, camera hash}. */
+int rt_nw_accum_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t H, int32_t row0,
+                     int32_t row_step, int32_t max_depth, uint64_t seed);
+int rt_nw_accum_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
+                     int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed, int32_t *spp_done);
+int rt_nw_accum_info(const char *path, int32_t out8[8], uint64_t out3[3]);
+/* Host only (no device needed): FNV-1a 64 over everything of the scene that
+ * can change a pixel, and nothing else — no address, not the accelerator
+ * setting, no BVH or grid.  The same value in any process that builds the
+ * scene with the same calls.  Serialisation (every number in its in-memory
+ * little-endian form; "table" = the record count as int64, then the records):
+ *   the bytes "RTMINWS1";
+ *   of the flat view at time 0 (rt_nw_scene_flat, rt_nw_flat's layouts): the
+ *     tables obj (16 words each, aux included: medium samples, twins), inst,
+ *     mat, tex, perlin_vec (floats), perlin_perm (int32), image_desc,
+ *     image_px (bytes); the three background floats;
+ *   the tables of the attribute records (16 words each, creation order) and of
+ *     the locator (one int32 per flattened object: its record or -1);
+ *   the placement count as int64, then per placement reached from the world,
+ *     in insertion order: int32 first, count, flags (1 moving | 2 affine);
+ *     moving: floats o0[3], o1[3], time0, time1 (rt_nw_move's composed ends);
+ *     affine: floats M[9] = float(A^-1) row-major and off[3] = float(b), the
+ *     rows the kernels read (the flat view only shows them baked).
+ * Taking the hash takes the flat view at time 0 and puts a view the caller
+ * held at another time back (its pointers are to be fetched again). */
+int rt_nw_scene_hash(rt_nw_scene *s, uint64_t *out);
 /* Debug (parity investigations): the path segments of ONE camera sample
  * (pixel i, j, sample s), up to cap: per segment 12 floats o.xyz, d.xyz, t,
  * the winner's insertion index (int32 bits, -1: miss), its hit-record normal
