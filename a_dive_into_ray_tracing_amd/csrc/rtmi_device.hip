@@ -80,6 +80,9 @@ struct RenderArgs {
   // and per-tile world.hit counts of this launch (null: not measured)
   const int32_t *tile_order;
   unsigned *tile_cost;
+  // tile lists: the cap on a list's entries, 0 (no lists) to
+  // kTileListCap (RTMI_TILE_LIST_MAX, read on the host)
+  int32_t tile_list_max;
 };
 
 #ifndef RTMI_WAVES_PER_BLOCK
@@ -294,8 +297,8 @@ template <int ACC, bool FIRST = false>
 __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const SpherePair *__restrict__ pairs,
                                              const RenderArgs &a, V3<float> &o, V3<float> &d, V3<float> &T,
                                              int &depth, Xoro &rng, V3<float> &col, SegCounters &cnt,
-                                             unsigned long long *segments) {
-  (void)cnt, (void)segments;
+                                             unsigned long long *segments, int32_t tile_list = -1) {
+  (void)cnt, (void)segments, (void)tile_list;
   float t;
 #if RTMI_TRACE
   const unsigned long long cyc0 = __builtin_amdgcn_s_memtime();
@@ -309,14 +312,15 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
 #endif
     );
   } else if constexpr (ACC >= 2) {
-    k = hit_world_grid<kBigGroup, acc_flat(ACC), acc_gmem(ACC)>(a.acc, o, d, t, key
+    // (the tile's list: a primary batch of the LDS grid kinds only)
+    k = hit_world_grid<kBigGroup, acc_flat(ACC), acc_gmem(ACC), FIRST && !acc_gmem(ACC)>(a.acc, o, d, t, key
 #if RTMI_STATS
                                    , cnt.bvh_stats
 #endif
 #if RTMI_TRACE_PHASES
                                    , cnt.pc
 #endif
-                                   );
+                                   , tile_list);
   } else {
     k = hit_world_packed<kPairGroup>(pairs, a.npairs, o, d, t
 #if RTMI_STATS
@@ -444,6 +448,44 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
   const int nv = vw * vh;  // valid pixels of this tile
   const int nq = nv * ns;  // jobs: (pixel, sample) pairs of this item
 
+  // The tile's list (the LDS grid kinds): every small sphere a
+  // camera ray of this tile can meet (tile_may_hit: a conservative test of the
+  // tile's ray bundle), as 16-bit record-slot keys in the dynamic LDS past the
+  // sums, 64 bytes per wave.  The item's primary batches then test these
+  // spheres in place of the grid walk.  Rounds of 64 spheres, the passing
+  // keys compacted by ballot; more than the cap, or an item of few samples
+  // (the 1-spp cost probe: the build costs about three passes): no list.
+  // One wave-uniform value (a scalar register held through the item): the
+  // list's LDS address x 64 + its length; < 0: no list, the batches walk the grid
+  int32_t tile_list = -1;
+  if constexpr (ACC == 2 || ACC == 3) {
+    uint16_t *const tl = reinterpret_cast<uint16_t *>(acc_lds + (acc_shared ? 1 : WPB) * 3 * 64) + wave * kTileListCap;
+    const int cap = min(a.tile_list_max, kTileListCap);
+    if (cap > 0 && ns >= kTileListMinSpp && a.acc.ntile > 0) {
+      const TileBundle tb = tile_bundle(a.cam, a.W, a.H, x0, vw, a.row0 + y0 * a.row_step,
+                                        a.row0 + (y0 + vh - 1) * a.row_step);
+      const uint32_t *const keys = reinterpret_cast<const uint32_t *>(a.acc.tile_sph + a.acc.ntile);
+      const int ln = int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+      int n = 0;
+      for (int i0 = 0; i0 < a.acc.ntile && n <= cap; i0 += 64) {
+        const int i = i0 + ln;
+        bool pass = false;
+        uint32_t key = 0u;
+        if (i < a.acc.ntile) {
+          const float4 s = a.acc.tile_sph[i];
+          key = keys[i];
+          pass = tile_may_hit(tb, s.x, s.y, s.z, s.w);
+        }
+        const unsigned long long m = __ballot(pass);
+        const int slot = n + int(__builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u)));
+        if (pass && slot < cap) tl[slot] = uint16_t(key);
+        n = __builtin_amdgcn_readfirstlane(n + __popcll(m));
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the wave's other lanes read the list
+      if (n <= cap) tile_list = __builtin_amdgcn_readfirstlane(int(lds_address(tl) << 6) | n);
+    }
+  }
+
   unsigned nseg = 0;  // world.hit calls of this wave (wave-uniform; algorithmic-work accounting)
   RTMI_TRACE_BEGIN
   SegCounters cnt{};
@@ -547,7 +589,7 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
         camera_ray(q, po, pd, prng);
         V3<float> unused_T = mk(1.f, 1.f, 1.f), col = mk(0.f, 0.f, 0.f);
         int hit = 0;
-        survives = !path_segment<ACC, true>(sc, pairs, a, po, pd, unused_T, hit, prng, col, cnt, segments);
+        survives = !path_segment<ACC, true>(sc, pairs, a, po, pd, unused_T, hit, prng, col, cnt, segments, tile_list);
         const int px = job_pixel(pbase + lane_now());  // (after the walk: not live through it)
         ptag = px | (hit << 6);
         if (!survives) {
@@ -1386,6 +1428,14 @@ struct rt_ctx {
   bool grid_ok = false;
   bool grid_global = false;  // the grid is walked in global memory (grid_gmem: its LDS image)
   char *grid_gmem = nullptr;
+  // tile lists: Accel::tile_sph, and the cap on a list's
+  // entries (RTMI_TILE_LIST_MAX, for A/B and tests: 0 = no lists, the
+  // primary batches walk the grid; 1 .. kTileListCap)
+  float4 *tile_sph = nullptr;
+  int32_t ntile = 0;
+  int32_t tile_list_max = std::getenv("RTMI_TILE_LIST_MAX")
+                              ? std::max(0, std::min(kTileListCap, std::atoi(std::getenv("RTMI_TILE_LIST_MAX"))))
+                              : kTileListCap;
   // RTMI_GRID_GLOBAL=1 (tests): the global-memory walk for any grid
   bool force_grid_global = std::getenv("RTMI_GRID_GLOBAL") && std::atoi(std::getenv("RTMI_GRID_GLOBAL")) != 0;
   // cost-ordered dispatch: per-tile world.hit counts of the
@@ -1541,7 +1591,7 @@ RTMI_EXPORT int rt_ctx_destroy(rt_ctx *ctx) {
                   (void *)ctx->big_pairs, (void *)ctx->big_idx, (void *)ctx->nodes, (void *)ctx->bvh_sph, (void *)ctx->bvh_idx,
                   (void *)ctx->cost_prev, (void *)ctx->cost_cur, (void *)ctx->cost_sorted, (void *)ctx->order,
                   (void *)ctx->iota, ctx->sort_tmp, (void *)ctx->grid_sph, (void *)ctx->grid_cells, (void *)ctx->grid_refs,
-                  (void *)ctx->grid_gmem})
+                  (void *)ctx->grid_gmem, (void *)ctx->tile_sph})
     if (p) (void)hipFree(p);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
@@ -1670,6 +1720,10 @@ struct GridBuild {
   std::vector<uint32_t> cells;  // ncells + 1: each cell's first reference
   std::vector<uint32_t> refs;   // 16 x scene index
   bool fits_lds = true;         // its LDS image fits the per-block budget (else: walked in global memory)
+  // tile lists (Accel::tile_sph): per small sphere {centre, grown radius} and a
+  // record slot of it / 16; empty when a slot number passes 16 bits
+  std::vector<float4> tile_sph;
+  std::vector<uint32_t> tile_keys;
 };
 bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, int32_t n, int32_t nbig_slots,
                 GridBuild &out) {
@@ -1749,10 +1803,40 @@ bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, int32_t 
   // 17.6 KB grid 1.05 ms in LDS vs 1.13 in global memory (config 2: 19.2 vs
   // 20.2 ms); 1 604 spheres (a 58 KB grid, 2 blocks per CU) 2.71 vs 1.13 ms.
   // RTMI_GRID_LDS_MAX overrides the byte limit (A/B).
+  // (the block's four tile lists, 2 kTileListCap bytes each, come out of the
+  // same budget)
   const char *lim_env = std::getenv("RTMI_GRID_LDS_MAX");
-  const size_t lds_max = lim_env && std::atoll(lim_env) > 0 ? size_t(std::atoll(lim_env)) : 160 * 1024 / 8 - 3 * 64 * 8 - 256;
+  const size_t lds_max = lim_env && std::atoll(lim_env) > 0
+                             ? size_t(std::atoll(lim_env))
+                             : 160 * 1024 / 8 - 3 * 64 * 8 - 256 - GridShape<true>::waves * 2 * kTileListCap;
   out.fits_lds = grid_lds_bytes(nbig_slots, out.desc.ncells, out.desc.nrefs) <= lds_max;
+  // The tile lists' table: the sphere with the radius the grid's cells list it
+  // by (its own margin, 1e-3 of its coordinate scale: the same distance from
+  // float error), rounded up, and the first record slot that holds it.
+  std::vector<uint32_t> first(size_t(n), UINT32_MAX);
+  for (size_t p = out.refs.size(); p-- > 0;) first[out.refs[p] >> 4] = uint32_t(nbig_slots) + uint32_t(p);
+  if (size_t(nbig_slots) + out.refs.size() <= 65536) {
+    for (int32_t k : small) {
+      const double *c = b.cr + 4 * k, R = std::fabs(c[3]) + b.margin(k);
+      float rg = float(R);
+      if (double(rg) < R) rg = std::nextafter(rg, INFINITY);
+      out.tile_sph.push_back(make_float4(float(c[0]), float(c[1]), float(c[2]), rg));
+      out.tile_keys.push_back(first[size_t(k)]);
+    }
+  }
   return true;
+}
+
+// The rows and columns of tile `tile` of a strip (render_kernel's item
+// geometry): columns [x0, x0 + vw), image rows j_lo .. j_hi
+void tile_extent(int32_t W, int32_t row0, int32_t row_step, int32_t nvalid, int32_t tw, int32_t tile, int32_t &x0,
+                 int32_t &vw, int32_t &j_lo, int32_t &j_hi) {
+  const int32_t th = 64 / tw, tiles_x = (W + tw - 1) / tw, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int32_t y0 = ty * th, vh = std::min(th, nvalid - y0);
+  x0 = tx * tw;
+  vw = std::min(tw, W - x0);
+  j_lo = row0 + y0 * row_step;
+  j_hi = row0 + (y0 + vh - 1) * row_step;
 }
 }  // namespace
 
@@ -1914,6 +1998,17 @@ RTMI_EXPORT int rt_ctx_set_scene(rt_ctx *ctx, const rt_scene *scene) {
       ctx->grid.refs = ctx->grid_refs;
       ctx->ngrid_sph = int32_t(gb.sph.size());
       ctx->grid_global = ctx->force_grid_global || !gb.fits_lds;
+      ctx->ntile = 0;
+      if (!ctx->grid_global && !gb.tile_sph.empty()) {
+        // {centre, grown radius} per small sphere, then the slot keys
+        const size_t ns = gb.tile_sph.size();
+        std::vector<float4> tab(ns + (ns + 3) / 4);
+        std::copy(gb.tile_sph.begin(), gb.tile_sph.end(), tab.begin());
+        std::memcpy(tab.data() + ns, gb.tile_keys.data(), ns * sizeof(uint32_t));
+        if ((rc = dev_alloc(&ctx->tile_sph, tab.size()))) return rc;
+        HIP_TRY(hipMemcpy(ctx->tile_sph, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        ctx->ntile = int32_t(ns);
+      }
       if (ctx->grid_global) {
         // the image stage_grid builds in LDS, offsets from 0: the slots (big
         // spheres, then every cell's references as copies of their spheres'
@@ -1963,9 +2058,10 @@ RTMI_EXPORT int rt_debug_grid_strides(const int32_t *n3, uint32_t *strides2) {
   return RT_OK;
 }
 
-RTMI_EXPORT int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint32_t *strides2, float *box6) {
-  if (!scene || scene->n <= 0 || !scene->center_radius || !dims3 || !strides2)
-    return set_error(RT_EINVAL, "rt_debug_grid_layout: bad argument");
+namespace {
+// The grid rt_ctx_set_scene builds for a scene, on the host alone (false: the
+// scene has none); nbs: the big spheres' record slots before the cells'
+bool host_grid(const rt_scene *scene, GridBuild &gb, int32_t &nbs) {
   const int n = scene->n;
   std::vector<float4> g(n, make_float4(0.f, 0.f, 0.f, 0.f));  // (build_grid copies the records; their values do not shape the grid)
   std::vector<double> rad(n);
@@ -1980,9 +2076,17 @@ RTMI_EXPORT int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint
     for (int a = 0; a < 3; ++a) scale = std::max(scale, std::fabs(scene->center_radius[4 * k + a]) + rad[k]);
   }
   BvhBuilder b{scene->center_radius, g, 1e-6 * scale, {}, {}, {}};
-  const int nb_pad = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
+  nbs = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
+  return !small.empty() && build_grid(b, small, n, nbs, gb);
+}
+}  // namespace
+
+RTMI_EXPORT int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint32_t *strides2, float *box6) {
+  if (!scene || scene->n <= 0 || !scene->center_radius || !dims3 || !strides2)
+    return set_error(RT_EINVAL, "rt_debug_grid_layout: bad argument");
   GridBuild gb;
-  if (small.empty() || !build_grid(b, small, n, nb_pad, gb)) return set_error(RT_EUNSUPPORTED, "no grid for this scene");
+  int32_t nb_pad;
+  if (!host_grid(scene, gb, nb_pad)) return set_error(RT_EUNSUPPORTED, "no grid for this scene");
   for (int a = 0; a < 3; ++a) dims3[a] = gb.desc.n[a];
   strides2[0] = gb.desc.row_bytes;
   strides2[1] = gb.desc.layer_bytes;
@@ -2031,6 +2135,45 @@ static int auto_tile_w(int32_t W, int32_t rows) {
   return idle(16) < idle(8) ? 16 : 8;
 }
 
+// Validation entry point (host only, no device): the tile lists render_kernel
+// builds, by the same tile_bundle / tile_may_hit, for the
+// strip of rows row0 + r row_step, r < nrows, of a W x H image in tiles of
+// tile_w x 64 / tile_w (0: the automatic shape).  tile >= 0: that tile's list
+// as scene indices in out_indices[cap] and its length in out_count[0]; tile
+// -1: every tile's, cap entries and one count each.  A count of -1: more than
+// cap spheres pass, the tile has no list (its batches walk the grid).
+RTMI_EXPORT int rt_debug_tile_list(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
+                                   int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t cap,
+                                   int32_t *out_indices, int32_t *out_count) {
+  if (!scene || scene->n <= 0 || !scene->center_radius || !camera || !out_indices || !out_count)
+    return set_error(RT_EINVAL, "rt_debug_tile_list: bad argument");
+  if (W < 2 || H < 2 || row0 < 0 || row0 >= H || row_step < 1 || nrows < 1 || cap < 1 || cap > kTileListCap ||
+      (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64))
+    return set_error(RT_EINVAL, "rt_debug_tile_list: bad image, strip, tile shape or cap");
+  const int32_t nvalid = int32_t(std::min<int64_t>(nrows, (int64_t(H) - row0 + row_step - 1) / row_step));
+  const int32_t tw = tile_w ? tile_w : auto_tile_w(W, nvalid), th = 64 / tw;
+  const int64_t tiles = int64_t((W + tw - 1) / tw) * ((nvalid + th - 1) / th);
+  if (tile < -1 || tile >= tiles) return set_error(RT_EINVAL, "rt_debug_tile_list: tile %d of %lld", tile, (long long)tiles);
+  GridBuild gb;
+  int32_t nbs;
+  if (!host_grid(scene, gb, nbs) || gb.tile_sph.empty()) return set_error(RT_EUNSUPPORTED, "no tile lists for this scene");
+  const Cam<float> cam = cam_f(camera);
+  for (int64_t t = tile < 0 ? 0 : tile, o = 0; t < (tile < 0 ? tiles : tile + 1); ++t, ++o) {
+    int32_t x0, vw, j_lo, j_hi, cnt = 0;
+    tile_extent(W, row0, row_step, nvalid, tw, int32_t(t), x0, vw, j_lo, j_hi);
+    const TileBundle tb = tile_bundle(cam, W, H, x0, vw, j_lo, j_hi);
+    for (size_t i = 0; i < gb.tile_sph.size(); ++i) {
+      const float4 s = gb.tile_sph[i];
+      if (!tile_may_hit(tb, s.x, s.y, s.z, s.w)) continue;
+      // the key names a record slot; the slot's reference names the sphere
+      if (cnt < cap) out_indices[o * cap + cnt] = int32_t(gb.refs[gb.tile_keys[i] - uint32_t(nbs)] >> 4);
+      ++cnt;
+    }
+    out_count[o] = cnt <= cap ? cnt : -1;
+  }
+  return RT_OK;
+}
+
 RTMI_EXPORT int rt_ctx_set_tuning(rt_ctx *ctx, int32_t tile_w, int32_t chunk) {
   if (!ctx) return set_error(RT_EINVAL, "null ctx");
   if (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64)
@@ -2066,6 +2209,8 @@ Accel accel_of(const rt_ctx *ctx, int kind) {
     a.nsph = ctx->ngrid_sph;
     a.grid = ctx->grid;
     a.grid_gmem = ctx->grid_global ? ctx->grid_gmem : nullptr;
+    a.tile_sph = ctx->tile_sph;
+    a.ntile = kind <= 3 ? ctx->ntile : 0;
   }
   return a;
 }
@@ -2088,7 +2233,9 @@ void launch_tw(bool chunked, dim3 grid, hipStream_t st, const rt_ctx *ctx, const
   // set per block with block_flush, else one per wave)
   RenderArgs b = a;
   b.acc_off = int32_t((accel_lds_bytes(a.acc, ACC) + 15) / 16 * 16);
-  const size_t lds = size_t(b.acc_off) + size_t(chunked && a.block_flush ? 1 : GridShape<ACC != 0>::waves) * 3 * 64 * 8;
+  // (the LDS grid kinds: and the waves' tile lists, render_kernel)
+  const size_t lds = size_t(b.acc_off) + size_t(chunked && a.block_flush ? 1 : GridShape<ACC != 0>::waves) * 3 * 64 * 8 +
+                     (ACC == 2 || ACC == 3 ? size_t(GridShape<true>::waves) * 2 * kTileListCap : 0);
   if (chunked)
     hipLaunchKernelGGL((render_kernel<TW, true, ACC>), grid, dim3(64 * GridShape<ACC != 0>::waves), lds, st, ctx->geom,
                        ctx->sh0, ctx->sh1, ctx->pairs, b, accum, out, ctx->segments);
@@ -2285,6 +2432,7 @@ int render_rows_impl(rt_ctx *ctx, const rt_camera *cam, int32_t W, int32_t H, in
     std::copy(sched, sched + 8, ctx->last_sched);
   }
   a.s_base = s_base;
+  a.tile_list_max = ctx->tile_list_max;
   a.out_elems = uint64_t(nvalid) * uint64_t(W) * 3;
   const size_t n_valid_out = size_t(nvalid) * W * 3;
   if (chunked && !pass_accum && !a.block_owns_tile) {

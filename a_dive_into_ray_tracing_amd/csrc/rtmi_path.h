@@ -486,7 +486,86 @@ struct Accel {
   // a grid over the LDS budget: the image stage_grid builds in LDS (slots,
   // cell starts, indices; offsets from 0) in global memory
   const char *grid_gmem;
+  // tile lists (the LDS grid kinds only): per small sphere
+  // {centre, grown radius} (tile_sphere_radius), and behind the ntile float4s
+  // one uint32 per sphere, a record slot of it (any: the slot names the
+  // record) as its offset from the first slot / 16.  ntile 0: no lists.
+  const float4 *tile_sph;
+  int32_t ntile;
 };
+
+// ---------------------------------------------------------------------------
+// tile lists: the small spheres a tile's camera rays can meet
+// ---------------------------------------------------------------------------
+// The camera rays of one tile — lens points o = origin + lens (px u + py v),
+// (px, py) in the unit disk, through F(s, t) = llc + s hor + t ver with (s, t)
+// in the tile's rectangle — as a cone of balls around one central ray: every
+// point of every such ray lies within rho + tau k of the central point
+// origin + tau e (tau >= 0 the distance along the unit axis e).  Host and
+// kernel run this same code (rt_debug_tile_list, render_kernel).
+struct TileBundle {
+  float ox, oy, oz;  // the camera origin
+  float ex, ey, ez;  // the axis: unit(Fc - origin), Fc the mean of F's four corners
+  float rho;         // the lens disk's radius in space, with the margins below
+  float k;           // (Rf + rho) / |Fc - origin|, Rf the largest corner distance from Fc, with the margins
+  float q;           // max(0, 1 - k^2)
+};
+constexpr int kTileListCap = 32;      // entries of a wave's list (16 bits each)
+constexpr int kTileListMinSpp = 4;    // items of fewer samples build no list (the 1-spp cost probe)
+
+// The tile of columns [x0, x0 + vw) and image rows j_lo .. j_hi (a strip's
+// rows lie row_step apart: any rows between them are covered too).  The
+// jitter is in [0, 1), so s spans [x0, x0 + vw] / (W - 1) and t
+// [j_lo, j_hi + 1] / (H - 1).
+__host__ __device__ inline TileBundle tile_bundle(const Cam<float> &c, int32_t W, int32_t H, int32_t x0, int32_t vw,
+                                                  int32_t j_lo, int32_t j_hi) {
+  const float s0 = float(x0) / float(W - 1), s1 = float(x0 + vw) / float(W - 1);
+  const float t0 = float(j_lo) / float(H - 1), t1 = float(j_hi + 1) / float(H - 1);
+  // F is affine in (s, t): Fc at the rectangle's centre, the corners at
+  // +-a +-b from it (a, b half the rectangle's sides in space)
+  const float sc = 0.5f * (s0 + s1), tc = 0.5f * (t0 + t1), sh = 0.5f * (s1 - s0), th = 0.5f * (t1 - t0);
+  const float dx = c.llc.x + sc * c.hor.x + tc * c.ver.x - c.origin.x;
+  const float dy = c.llc.y + sc * c.hor.y + tc * c.ver.y - c.origin.y;
+  const float dz = c.llc.z + sc * c.hor.z + tc * c.ver.z - c.origin.z;
+  const float ax = sh * c.hor.x, ay = sh * c.hor.y, az = sh * c.hor.z;
+  const float bx = th * c.ver.x, by = th * c.ver.y, bz = th * c.ver.z;
+  const float aa = ax * ax + ay * ay + az * az, bb = bx * bx + by * by + bz * bz, ab = ax * bx + ay * by + az * bz;
+  const float rf = sqrtf(aa + bb + 2.0f * fabsf(ab));  // max |+-a +-b|
+  // |px u + py v|^2 <= the larger eigenvalue of [[u.u, u.v], [u.v, v.v]] on the unit disk
+  const float uu = c.u.x * c.u.x + c.u.y * c.u.y + c.u.z * c.u.z, vv = c.v.x * c.v.x + c.v.y * c.v.y + c.v.z * c.v.z;
+  const float uv = c.u.x * c.v.x + c.u.y * c.v.y + c.u.z * c.v.z;
+  const float hd = 0.5f * (uu - vv);
+  const float rho = fabsf(c.lens) * sqrtf(0.5f * (uu + vv) + sqrtf(hd * hd + uv * uv));
+  const float len = sqrtf(dx * dx + dy * dy + dz * dz), inv = 1.0f / len;
+  TileBundle b;
+  b.ox = c.origin.x; b.oy = c.origin.y; b.oz = c.origin.z;
+  b.ex = dx * inv; b.ey = dy * inv; b.ez = dz * inv;
+  // Margins that dwarf float error (the rays the kernel forms differ from the
+  // ideal ones by ~1e-6 of the coordinates' scale): 1e-3 relative on the whole
+  // bound, and 1e-5 of the origin's scale and of the distance along the axis
+  const float on = fmaxf(fmaxf(fabsf(c.origin.x), fabsf(c.origin.y)), fabsf(c.origin.z));
+  b.rho = 1.001f * rho + 1e-5f * (1.0f + on);
+  b.k = 1.001f * ((rf + rho) * inv) + 1e-5f;
+  b.q = fmaxf(0.0f, 1.0f - b.k * b.k);
+  return b;
+}
+
+// Whether a ray of the bundle can meet the sphere (centre, radius rg: the
+// grown radius, tile_sphere_radius).  With tau_c = max(0, (c - origin).e) and
+// h the distance from c to the axis point at tau_c, every ball of the cone
+// lies in h sqrt(1 - k^2) <= rg + rho + k tau_c; the test
+// passes unless that fails, so a NaN (a degenerate camera) or k >= 1 (a huge
+// aperture, a tiny image: q = 0) passes everything.  Conservative only: it
+// adds spheres to a list, it never decides a hit.
+__host__ __device__ inline bool tile_may_hit(const TileBundle &b, float cx, float cy, float cz, float rg) {
+  const float px = cx - b.ox, py = cy - b.oy, pz = cz - b.oz;
+  const float al = px * b.ex + py * b.ey + pz * b.ez;
+  const float tau = fmaxf(al, 0.0f);
+  const float qx = px - tau * b.ex, qy = py - tau * b.ey, qz = pz - tau * b.ez;
+  const float h2 = qx * qx + qy * qy + qz * qz;
+  const float rhs = rg + b.rho + b.k * tau;
+  return !(h2 * b.q > rhs * rhs);
+}
 
 // big_idx through the constant address space: wave-uniform scalar loads
 __device__ __forceinline__ int32_t big_index(const Accel &a, int slot) {
@@ -763,7 +842,14 @@ __device__ __forceinline__ void hit_big(const Accel &acc_s, V3<float> d, float K
 // each time.  FLAT_Y: the grid has one cell layer in y (the final scene's
 // 20 x 1 x 20) — the same walk with the y axis' stepping state dropped: a y
 // face only ends the walk (5 VGPRs fewer in the loop).
-template <int GP, bool FLAT_Y = false, bool GMEM = false>
+// LIST (a primary batch's camera rays): tile_list >= 0 — the
+// wave's tile has a list (its LDS address x 64 + its length, at most
+// kTileListCap) of 16-bit record-slot keys that names every small sphere a
+// camera ray of the tile can meet (tile_may_hit) — tests those spheres in one
+// wave-uniform loop in place of the clip and the walk: the same arithmetic,
+// acceptance and tie rule, so the same hit and the same hit_key.
+// tile_list < 0: the walk.
+template <int GP, bool FLAT_Y = false, bool GMEM = false, bool LIST = false>
 __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> o, V3<float> d, float &t_hit,
                                                   uint32_t &hit_key
 #if RTMI_STATS
@@ -772,7 +858,8 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
 #if RTMI_TRACE_PHASES
                                                   , PhaseClock &pc
 #endif
-                                                  ) {
+                                                  , int32_t tile_list = -1) {
+  static_assert(!(LIST && GMEM), "tile lists name LDS record slots");
 #if RTMI_TRACE_PHASES
   const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -807,145 +894,165 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
   pc.c[0] += tp1 - tp0;
   unsigned long long tp2 = tp1;
 #endif
-  const GridDesc &G = rtmi_grid_desc;  // (stage_grid)
-  const float ix = safe_inv<FLAT_Y>(d.x), iy = safe_inv<FLAT_Y>(d.y), iz = safe_inv<FLAT_Y>(d.z);
-  const float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
-  // the grid box, clipped to [0, t_max]
-  const float bx0 = __builtin_fmaf(G.g0[0], ix, ox), bx1 = __builtin_fmaf(G.g1[0], ix, ox);
-  const float by0 = __builtin_fmaf(G.g0[1], iy, oy), by1 = __builtin_fmaf(G.g1[1], iy, oy);
-  const float bz0 = __builtin_fmaf(G.g0[2], iz, oz), bz1 = __builtin_fmaf(G.g1[2], iz, oz);
-  const float tnear = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(bx0, bx1), __builtin_fminf(by0, by1)),
-                                      __builtin_fmaxf(__builtin_fminf(bz0, bz1), 0.0f));
-  const float tfar = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(bx0, bx1), __builtin_fmaxf(by0, by1)),
-                                     __builtin_fminf(__builtin_fmaxf(bz0, bz1), t_max));
-  if (tnear <= tfar) {
-    const uint32_t cells = base + G.cells_off;
-    // entry cell: the cell of o + tnear*d, clamped into the grid.
-    // The floored coordinate is clamped as a float (one v_med3_f32), and t0
-    // and kmax are formed from that float: it is an integer below 2^16, so
-    // c + 1 and n - 1 - c are exact in float and equal the conversions of the
-    // integer forms bit for bit.  One conversion per axis remains, for the
-    // address.  (A NaN coordinate: the integer conversion gave cell 0; med3
-    // gives the smaller bound, 0, as well.)
-    auto cell_of = [&](float p, int ax) {
-      return __builtin_amdgcn_fmed3f(__builtin_floorf((p - G.g0[ax]) * G.inv_h[ax]), 0.0f, G.nm1[ax]);
-    };
-    const float fx = cell_of(__builtin_fmaf(tnear, d.x, o.x), 0);
-    const float fy = FLAT_Y ? 0.0f : cell_of(__builtin_fmaf(tnear, d.y, o.y), 1);
-    const float fz = cell_of(__builtin_fmaf(tnear, d.z, o.z), 2);
-    const int cx = int(fx), cy = int(fy), cz = int(fz);
-    // Per axis: after k steps on it the current cell's far face lies at
-    // t = fma(k, dt, t0) (t0 the entry cell's far face, dt = h/|d_axis|), and
-    // the walk leaves the grid when it would step past kmax.  (Only which
-    // cells are visited depends on these roundings, never a hit: DESIGN.md
-    // §4.5's argument needs face parameters within ~1e-6 of the truth, the
-    // margins being >= 1e-3.)
-    float t0x, t0y, t0z, dtx, dty, dtz, kmx, kmy, kmz;
-    // The step direction comes from the culling inverse, not from d: safe_inv
-    // gives -0.0 the inverse -1e20, so `d >= 0` (true for -0.0) would pick the
-    // far face on the wrong side and step into cells the ray never enters.
-    auto axis = [&](float inv, float oo, float cf, int ax, float &t0, float &dt, float &kmax) {
-      const bool pos = inv >= 0.0f;
-      t0 = __builtin_fmaf(__builtin_fmaf(pos ? cf + 1.0f : cf, G.h[ax], G.g0[ax]), inv, oo);
-      dt = __builtin_fabsf(G.h[ax] * inv);
-      kmax = pos ? G.nm1[ax] - cf : cf;
-    };
-    axis(ix, ox, fx, 0, t0x, dtx, kmx);
-    if constexpr (FLAT_Y) {  // the one layer's far y face (axis() at c = 0, no steps)
-      t0y = __builtin_fmaf(__builtin_fmaf(iy >= 0.0f ? 1.0f : 0.0f, G.h[1], G.g0[1]), iy, oy);
-      dty = kmy = 0.0f;
-    } else {
-      axis(iy, oy, fy, 1, t0y, dty, kmy);
-    }
-    axis(iz, oz, fz, 2, t0z, dtz, kmz);
-    float kx = 0.0f, ky = 0.0f, kz = 0.0f, tnx = t0x, tny = t0y, tnz = t0z;
-    // the LDS address of the current cell's start, stepped by 4 x the cell step:
-    // by the descriptor's byte strides and 24-bit multiplies (grid_strides);
-    // the one-layer walk has cy = 0 and no y step
-    uint32_t cell = cells + 4u * uint32_t(cx) + __umul24(uint32_t(cz), G.layer_bytes);
-    if constexpr (!FLAT_Y) cell += __umul24(uint32_t(cy), G.row_bytes);
-    const int dcx = ix >= 0.0f ? 4 : -4;
-    const int dcy = FLAT_Y ? 0 : (iy >= 0.0f ? int(G.row_bytes) : -int(G.row_bytes));
-    const int dcz = iz >= 0.0f ? int(G.layer_bytes) : -int(G.layer_bytes);
-#if RTMI_TRACE_PHASES
-    tp2 = __builtin_amdgcn_s_memtime();
-#endif
-    for (;;) {
+  if (LIST && tile_list >= 0) {
+    const uint32_t tl = uint32_t(tile_list) >> 6, tl_end = tl + 2u * (uint32_t(tile_list) & 63u);
+    for (uint32_t e = tl; e < tl_end; e += 2u) {
+      // the key made scalar: the record's address is the same in every lane
+      const uint32_t key = base + 16u * uint32_t(__builtin_amdgcn_readfirstlane(int(lds_u16(e))));
 #if RTMI_STATS
-      gstats[0] += 1;
-      if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[2] += 1;
+      gstats[1] += 1;
+      if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[3] += 1;
 #endif
-      const uint32_t re = rd_u32(cell + 4u);  // (with the next one: a ds_read2_b32)
-      // Deferred root resolution: a lane keeps its first candidate of the
-      // cell and resolves it after the cell's sphere loop (a second candidate
-      // resolves the kept one first).  A wave then runs the resolution about
-      // once per cell instead of at every sphere where some lane has a
-      // candidate (tools/grid_sim.c: 3.4 instead of 4.8 per wave-segment).
-      // The result is the same: resolve_root's acceptance is order-independent
-      // (the closest root, ties to the larger index), and the walk's exit
-      // test comes after the cell's resolutions either way.  (kNoKey: none —
-      // an explicit sentinel no LDS address can take, not 0, which slot 0
-      // would be if nothing preceded the dynamic LDS)
-      constexpr uint32_t kNoKey = 0xFFFFFFFFu;
-      uint32_t kaddr = kNoKey;
-      float khb = 0.0f, kdisc = 0.0f;
-      for (uint32_t r = rd_u32(cell); r < re; r += 16u) {
-#if RTMI_STATS
-        gstats[1] += 1;
-        if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[3] += 1;
-#endif
-        float hb, disc;
-        sphere_test(rd_sphere(r), d, K, a, aL, mx, my, mz, hb, disc);
-        if (!(disc < 0.0f)) {
-          if (kaddr != kNoKey) {
-#if RTMI_STATS
-            if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[4] += 1;
-#endif
-            resolve_key<GMEM>(kaddr, khb, kdisc, inv_a, t_max, best_a, idx_base, gm);
-          }
-          kaddr = r;
-          khb = hb;
-          kdisc = disc;
-        }
-      }
-      if (kaddr != kNoKey) {
+      float hb, disc;
+      sphere_test(rd_sphere(key), d, K, a, aL, mx, my, mz, hb, disc);
+      if (!(disc < 0.0f)) {
 #if RTMI_STATS
         if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[4] += 1;
 #endif
-        resolve_key<GMEM>(kaddr, khb, kdisc, inv_a, t_max, best_a, idx_base, gm);
+        resolve_key<GMEM>(key, hb, disc, inv_a, t_max, best_a, idx_base, gm);
       }
-      const float texit = __builtin_fminf(tnx, __builtin_fminf(tny, tnz));
-      if constexpr (FLAT_Y) {
-        // the same step without nested branches: x when its face is nearest
-        // (ties to x), the y face ends the walk, else z (selects: 19.92 vs
-        // 20.06 ms, profiles/r03/ab_dda_select_shade_uniform.txt)
-        const bool sx = (tnx <= tny) & (tnx <= tnz);
-        const bool sy = !sx & (tny <= tnz);
-        const bool leave = !(texit < t_max) | sy | ((sx ? kx : kz) >= (sx ? kmx : kmz));
-        if (leave) break;
-        kx = sx ? kx + 1.0f : kx;
-        kz = sx ? kz : kz + 1.0f;
-        tnx = sx ? __builtin_fmaf(kx, dtx, t0x) : tnx;
-        tnz = sx ? tnz : __builtin_fmaf(kz, dtz, t0z);
-        cell += sx ? dcx : dcz;
-        continue;
-      }
-      if (!(texit < t_max)) break;  // the closest hit so far lies in the cells walked
-      if (tnx <= tny && tnx <= tnz) {
-        if (kx >= kmx) break;  // leaves the grid
-        kx += 1.0f;
-        tnx = __builtin_fmaf(kx, dtx, t0x);
-        cell += dcx;
-      } else if (tny <= tnz) {
-        if (FLAT_Y || ky >= kmy) break;  // leaves the grid
-        ky += 1.0f;
-        tny = __builtin_fmaf(ky, dty, t0y);
-        cell += dcy;
+    }
+  } else {
+    const GridDesc &G = rtmi_grid_desc;  // (stage_grid)
+    const float ix = safe_inv<FLAT_Y>(d.x), iy = safe_inv<FLAT_Y>(d.y), iz = safe_inv<FLAT_Y>(d.z);
+    const float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
+    // the grid box, clipped to [0, t_max]
+    const float bx0 = __builtin_fmaf(G.g0[0], ix, ox), bx1 = __builtin_fmaf(G.g1[0], ix, ox);
+    const float by0 = __builtin_fmaf(G.g0[1], iy, oy), by1 = __builtin_fmaf(G.g1[1], iy, oy);
+    const float bz0 = __builtin_fmaf(G.g0[2], iz, oz), bz1 = __builtin_fmaf(G.g1[2], iz, oz);
+    const float tnear = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(bx0, bx1), __builtin_fminf(by0, by1)),
+                                        __builtin_fmaxf(__builtin_fminf(bz0, bz1), 0.0f));
+    const float tfar = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(bx0, bx1), __builtin_fmaxf(by0, by1)),
+                                       __builtin_fminf(__builtin_fmaxf(bz0, bz1), t_max));
+    if (tnear <= tfar) {
+      const uint32_t cells = base + G.cells_off;
+      // entry cell: the cell of o + tnear*d, clamped into the grid.
+      // The floored coordinate is clamped as a float (one v_med3_f32), and t0
+      // and kmax are formed from that float: it is an integer below 2^16, so
+      // c + 1 and n - 1 - c are exact in float and equal the conversions of the
+      // integer forms bit for bit.  One conversion per axis remains, for the
+      // address.  (A NaN coordinate: the integer conversion gave cell 0; med3
+      // gives the smaller bound, 0, as well.)
+      auto cell_of = [&](float p, int ax) {
+        return __builtin_amdgcn_fmed3f(__builtin_floorf((p - G.g0[ax]) * G.inv_h[ax]), 0.0f, G.nm1[ax]);
+      };
+      const float fx = cell_of(__builtin_fmaf(tnear, d.x, o.x), 0);
+      const float fy = FLAT_Y ? 0.0f : cell_of(__builtin_fmaf(tnear, d.y, o.y), 1);
+      const float fz = cell_of(__builtin_fmaf(tnear, d.z, o.z), 2);
+      const int cx = int(fx), cy = int(fy), cz = int(fz);
+      // Per axis: after k steps on it the current cell's far face lies at
+      // t = fma(k, dt, t0) (t0 the entry cell's far face, dt = h/|d_axis|), and
+      // the walk leaves the grid when it would step past kmax.  (Only which
+      // cells are visited depends on these roundings, never a hit: DESIGN.md
+      // §4.5's argument needs face parameters within ~1e-6 of the truth, the
+      // margins being >= 1e-3.)
+      float t0x, t0y, t0z, dtx, dty, dtz, kmx, kmy, kmz;
+      // The step direction comes from the culling inverse, not from d: safe_inv
+      // gives -0.0 the inverse -1e20, so `d >= 0` (true for -0.0) would pick the
+      // far face on the wrong side and step into cells the ray never enters.
+      auto axis = [&](float inv, float oo, float cf, int ax, float &t0, float &dt, float &kmax) {
+        const bool pos = inv >= 0.0f;
+        t0 = __builtin_fmaf(__builtin_fmaf(pos ? cf + 1.0f : cf, G.h[ax], G.g0[ax]), inv, oo);
+        dt = __builtin_fabsf(G.h[ax] * inv);
+        kmax = pos ? G.nm1[ax] - cf : cf;
+      };
+      axis(ix, ox, fx, 0, t0x, dtx, kmx);
+      if constexpr (FLAT_Y) {  // the one layer's far y face (axis() at c = 0, no steps)
+        t0y = __builtin_fmaf(__builtin_fmaf(iy >= 0.0f ? 1.0f : 0.0f, G.h[1], G.g0[1]), iy, oy);
+        dty = kmy = 0.0f;
       } else {
-        if (kz >= kmz) break;
-        kz += 1.0f;
-        tnz = __builtin_fmaf(kz, dtz, t0z);
-        cell += dcz;
+        axis(iy, oy, fy, 1, t0y, dty, kmy);
+      }
+      axis(iz, oz, fz, 2, t0z, dtz, kmz);
+      float kx = 0.0f, ky = 0.0f, kz = 0.0f, tnx = t0x, tny = t0y, tnz = t0z;
+      // the LDS address of the current cell's start, stepped by 4 x the cell step:
+      // by the descriptor's byte strides and 24-bit multiplies (grid_strides);
+      // the one-layer walk has cy = 0 and no y step
+      uint32_t cell = cells + 4u * uint32_t(cx) + __umul24(uint32_t(cz), G.layer_bytes);
+      if constexpr (!FLAT_Y) cell += __umul24(uint32_t(cy), G.row_bytes);
+      const int dcx = ix >= 0.0f ? 4 : -4;
+      const int dcy = FLAT_Y ? 0 : (iy >= 0.0f ? int(G.row_bytes) : -int(G.row_bytes));
+      const int dcz = iz >= 0.0f ? int(G.layer_bytes) : -int(G.layer_bytes);
+#if RTMI_TRACE_PHASES
+      tp2 = __builtin_amdgcn_s_memtime();
+#endif
+      for (;;) {
+#if RTMI_STATS
+        gstats[0] += 1;
+        if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[2] += 1;
+#endif
+        const uint32_t re = rd_u32(cell + 4u);  // (with the next one: a ds_read2_b32)
+        // Deferred root resolution: a lane keeps its first candidate of the
+        // cell and resolves it after the cell's sphere loop (a second candidate
+        // resolves the kept one first).  A wave then runs the resolution about
+        // once per cell instead of at every sphere where some lane has a
+        // candidate (tools/grid_sim.c: 3.4 instead of 4.8 per wave-segment).
+        // The result is the same: resolve_root's acceptance is order-independent
+        // (the closest root, ties to the larger index), and the walk's exit
+        // test comes after the cell's resolutions either way.  (kNoKey: none —
+        // an explicit sentinel no LDS address can take, not 0, which slot 0
+        // would be if nothing preceded the dynamic LDS)
+        constexpr uint32_t kNoKey = 0xFFFFFFFFu;
+        uint32_t kaddr = kNoKey;
+        float khb = 0.0f, kdisc = 0.0f;
+        for (uint32_t r = rd_u32(cell); r < re; r += 16u) {
+#if RTMI_STATS
+          gstats[1] += 1;
+          if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[3] += 1;
+#endif
+          float hb, disc;
+          sphere_test(rd_sphere(r), d, K, a, aL, mx, my, mz, hb, disc);
+          if (!(disc < 0.0f)) {
+            if (kaddr != kNoKey) {
+#if RTMI_STATS
+              if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[4] += 1;
+#endif
+              resolve_key<GMEM>(kaddr, khb, kdisc, inv_a, t_max, best_a, idx_base, gm);
+            }
+            kaddr = r;
+            khb = hb;
+            kdisc = disc;
+          }
+        }
+        if (kaddr != kNoKey) {
+#if RTMI_STATS
+          if (__lane_id() == __builtin_ctzll(__ballot(1))) gstats[4] += 1;
+#endif
+          resolve_key<GMEM>(kaddr, khb, kdisc, inv_a, t_max, best_a, idx_base, gm);
+        }
+        const float texit = __builtin_fminf(tnx, __builtin_fminf(tny, tnz));
+        if constexpr (FLAT_Y) {
+          // the same step without nested branches: x when its face is nearest
+          // (ties to x), the y face ends the walk, else z (selects: 19.92 vs
+          // 20.06 ms, profiles/r03/ab_dda_select_shade_uniform.txt)
+          const bool sx = (tnx <= tny) & (tnx <= tnz);
+          const bool sy = !sx & (tny <= tnz);
+          const bool leave = !(texit < t_max) | sy | ((sx ? kx : kz) >= (sx ? kmx : kmz));
+          if (leave) break;
+          kx = sx ? kx + 1.0f : kx;
+          kz = sx ? kz : kz + 1.0f;
+          tnx = sx ? __builtin_fmaf(kx, dtx, t0x) : tnx;
+          tnz = sx ? tnz : __builtin_fmaf(kz, dtz, t0z);
+          cell += sx ? dcx : dcz;
+          continue;
+        }
+        if (!(texit < t_max)) break;  // the closest hit so far lies in the cells walked
+        if (tnx <= tny && tnx <= tnz) {
+          if (kx >= kmx) break;  // leaves the grid
+          kx += 1.0f;
+          tnx = __builtin_fmaf(kx, dtx, t0x);
+          cell += dcx;
+        } else if (tny <= tnz) {
+          if (FLAT_Y || ky >= kmy) break;  // leaves the grid
+          ky += 1.0f;
+          tny = __builtin_fmaf(ky, dty, t0y);
+          cell += dcy;
+        } else {
+          if (kz >= kmz) break;
+          kz += 1.0f;
+          tnz = __builtin_fmaf(kz, dtz, t0z);
+          cell += dcz;
+        }
       }
     }
   }

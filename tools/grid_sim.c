@@ -28,6 +28,9 @@
  *   (PRIMARY_BATCH=1: only the primary-batch model, DESIGN.md section 4.5: camera segments in path order
  *   in groups of 64 and secondary segments in groups of 64 against today's mixed groups, with 0 / 40 / 80 /
  *   120 extra instructions per batch pass; profiles/r07/primary_batch/grid_sim_primary_batch.txt)
+ *   (TILE_LIST=1: only the tile-list model, DESIGN.md section 4.5: per tile the small spheres its camera rays can
+ *   meet, by the kernel's bound in double; a batch pass that tests that list against today's clip + walk;
+ *   profiles/r09/tile_list/grid_sim_tile_list.txt)
  */
 #include <math.h>
 #include <stdio.h>
@@ -51,6 +54,7 @@ typedef struct { double o[3], d[3]; int depth, path; } Ray;
 static unsigned long long *g_cand, *g_use;
 static Ray *segs; static int nseg, capseg, cur_depth, cur_path;
 static int *tile_start; static int ntiles, captiles;
+static int *tile_tx, *tile_ty;  /* the simulated tiles' coordinates (in tiles) */
 
 static int hit_bf(const double o[3], const double d[3], double *tt) {
   double tmax = INFINITY; int best = -1;
@@ -430,7 +434,9 @@ int main(int argc, char **argv) {
   double lens = 0.05;
   int Wd = 1200, Ht = 800, spp = argc > 2 ? atoi(argv[2]) : 16, stride = argc > 3 ? atoi(argv[3]) : 7;
   for (int ty = 0; ty < Ht/8; ty += stride) for (int tx = 0; tx < Wd/8; tx += stride) {
-    if (ntiles + 1 >= captiles) { captiles = captiles ? 2*captiles : 1024; tile_start = realloc(tile_start, captiles*sizeof(int)); }
+    if (ntiles + 1 >= captiles) { captiles = captiles ? 2*captiles : 1024; tile_start = realloc(tile_start, captiles*sizeof(int));
+      tile_tx = realloc(tile_tx, captiles*sizeof(int)); tile_ty = realloc(tile_ty, captiles*sizeof(int)); }
+    tile_tx[ntiles] = tx; tile_ty[ntiles] = ty;
     int start = tile_start[ntiles++] = nseg;
     for (int s = 0; s < spp; s++) for (int p = 0; p < 64; p++) {
       int i = tx*8 + p%8, j = ty*8 + p/8;
@@ -562,6 +568,86 @@ int main(int argc, char **argv) {
     printf("\n");
   }
   if (getenv("CI_REST")) CI_REST = atof(getenv("CI_REST"));
+  if (getenv("TILE_LIST")) {
+    /* Tile lists.  Per simulated tile the list by the
+     * kernel's bound (tile_bundle / tile_may_hit of rtmi_path.h, in double, the
+     * same margins: the grid's grown radius, 1e-3 relative, 1e-5 of the
+     * scales).  A batch pass = 64 camera segments of one tile in path order
+     * (as PRIMARY_BATCH).  Today it pays the clip + DDA setup (CI_CLIP: ~80
+     * instructions counted in hit_world_grid's one-layer form: three safe_inv,
+     * the box clip's 6 fma + 12 min/max, the entry cell, t0 / dt / kmax of two
+     * axes, the cell address) and its walk (walk_instr); with a list, per
+     * listed sphere CI_LSPH (key read made scalar, record read, 8 fma,
+     * compare: 16) and a resolution (CI_RES) where any lane has a candidate,
+     * plus the item's list build (CI_BUILD ~400: 8 rounds of ~40 and the
+     * bundle) spread over the item's batches (125 at config 2).  A tile over
+     * the cap keeps today's cost.  Everything else in a pass is unchanged:
+     * all passes = the batch passes and the secondary-only passes (the tile's
+     * other segments in their shuffled order in groups of 64), CI_REST (which
+     * holds the clip) + the walk each. */
+    const double CI_CLIP = 80, CI_LSPH = 16, CI_BUILD = 400, ITEM_BATCHES = 125;
+    const int cap = getenv("TILE_LIST_MAX") ? atoi(getenv("TILE_LIST_MAX")) : 32;
+    double scene_scale = 0;
+    for (int k = 0; k < N; k++) for (int a = 0; a < 3; a++) { double v = fabs(C[k][a]) + fabs(C[k][3]); if (v > scene_scale) scene_scale = v; }
+    double uu = 0, vv = 0, uv = 0, on = 0;
+    for (int a = 0; a < 3; a++) { uu += cu[a]*cu[a]; vv += cv[a]*cv[a]; uv += cu[a]*cv[a]; if (fabs(org[a]) > on) on = fabs(org[a]); }
+    const double rho0 = lens * sqrt(0.5*(uu+vv) + sqrt(0.25*(uu-vv)*(uu-vv) + uv*uv));
+    long hist[34] = {0}; double sumlen = 0; int maxlen = 0, over = 0;
+    double today = 0, listed = 0, mixed = 0, mpass = 0, batches = 0, lsph = 0, lres = 0, missed = 0;
+    int *pr = malloc(nseg * sizeof(int)), *se = malloc(nseg * sizeof(int)), *list = malloc(nsmall * sizeof(int));
+    for (int t = 0; t < ntiles; t++) {
+      /* the bundle of tile (tx, ty): s in [8 tx, 8 tx + 8] / (W - 1), t in [8 ty, 8 ty + 8] / (H - 1) */
+      const double s0 = 8.0*tile_tx[t]/(Wd-1), s1 = (8.0*tile_tx[t]+8)/(Wd-1), t0 = 8.0*tile_ty[t]/(Ht-1), t1 = (8.0*tile_ty[t]+8)/(Ht-1);
+      double D[3], A[3], B[3], aa = 0, bb = 0, ab = 0, len = 0;
+      for (int a = 0; a < 3; a++) { D[a] = llc[a] + 0.5*(s0+s1)*hor[a] + 0.5*(t0+t1)*ver[a] - org[a]; A[a] = 0.5*(s1-s0)*hor[a]; B[a] = 0.5*(t1-t0)*ver[a];
+        aa += A[a]*A[a]; bb += B[a]*B[a]; ab += A[a]*B[a]; len += D[a]*D[a]; }
+      len = sqrt(len);
+      const double rf = sqrt(aa + bb + 2*fabs(ab)), rho = 1.001*rho0 + 1e-5*(1 + on), kk = 1.001*(rf + rho0)/len + 1e-5;
+      const double q = 1 - kk*kk > 0 ? 1 - kk*kk : 0;
+      int nl = 0;
+      for (int i = 0; i < nsmall; i++) { const int k = small_[i];
+        double m0 = 0; for (int a = 0; a < 3; a++) if (fabs(C[k][a]) > m0) m0 = fabs(C[k][a]);
+        const double rg = fabs(C[k][3]) + 1e-3*(1 + m0 + fabs(C[k][3])) + 1e-6*scene_scale;
+        double al = 0, P[3]; for (int a = 0; a < 3; a++) { P[a] = C[k][a] - org[a]; al += P[a]*D[a]/len; }
+        const double tau = al > 0 ? al : 0; double h2 = 0;
+        for (int a = 0; a < 3; a++) { const double x = P[a] - tau*D[a]/len; h2 += x*x; }
+        const double rhs = rg + rho + kk*tau;
+        if (!(h2*q > rhs*rhs)) list[nl++] = k; }
+      const int has_list = nl <= cap;
+      hist[nl > 33 ? 33 : nl]++; sumlen += nl; if (nl > maxlen) maxlen = nl; over += !has_list;
+      /* the tile's passes: camera segments in path order, and today's mixed groups for the total */
+      int np = 0, ns = 0;
+      for (int i = tile_start[t]; i < tile_start[t + 1]; i++) { if (segs[i].depth == 0) pr[np++] = i; else se[ns++] = i; }
+      for (int i = 1; i < np; i++) { const int x = pr[i]; int j = i - 1;
+        while (j >= 0 && segs[pr[j]].path > segs[x].path) { pr[j + 1] = pr[j]; j--; } pr[j + 1] = x; }
+      for (int i = 0; i < ns; i += 64) { mixed += CI_REST + walk_instr(se + i, ns - i < 64 ? ns - i : 64, NULL); mpass++; }
+      for (int i = 0; i < np; i += 64) { const int nb = np - i < 64 ? np - i : 64;
+        const double w = CI_CLIP + walk_instr(pr + i, nb, NULL);
+        double c = CI_BUILD / ITEM_BATCHES;
+        for (int j = 0; j < nl; j++) { const int k = list[j]; int any = 0;
+          for (int l = 0; l < nb && !any; l++) { const Ray *r = &segs[pr[i + l]];
+            double a2 = 0, hb = 0, cc = 0; for (int a = 0; a < 3; a++) { const double oc = r->o[a] - C[k][a]; a2 += r->d[a]*r->d[a]; hb += oc*r->d[a]; cc += oc*oc; }
+            if (hb*hb - a2*(cc - C[k][3]*C[k][3]) >= 0) any = 1; }
+          c += CI_LSPH + (any ? CI_RES : 0); lsph++; lres += any; }
+        /* check: a small sphere a camera ray of the batch meets and the list lacks */
+        for (int l = 0; l < nb; l++) { const Ray *r = &segs[pr[i + l]];
+          for (int s = 0; s < nsmall; s++) { const int k = small_[s];
+            double a2 = 0, hb = 0, cc = 0; for (int a = 0; a < 3; a++) { const double oc = r->o[a] - C[k][a]; a2 += r->d[a]*r->d[a]; hb += oc*r->d[a]; cc += oc*oc; }
+            cc -= C[k][3]*C[k][3];
+            if (hb*hb - a2*cc >= 0 && (hb < 0 || cc < 0)) { int in = 0; for (int j = 0; j < nl; j++) in |= list[j] == k; missed += !in; } } }
+        today += w; listed += has_list ? c : w; batches++; mixed += CI_REST - CI_CLIP + w; mpass++; }
+    }
+    printf("  tile lists (cap %d): %d tiles, mean %.2f, max %d, empty %.3f, over the cap %d; lengths 0..9:", cap, ntiles, sumlen / ntiles,
+           maxlen, (double)hist[0] / ntiles, over);
+    for (int k = 0; k < 10; k++) printf(" %.3f", (double)hist[k] / ntiles);
+    printf("\n  spheres met by a camera ray and not in its tile's list: %.0f\n", missed);
+    printf("  batch passes %.0f: per pass %.2f listed spheres, %.2f with a candidate (a resolution)\n", batches, lsph / batches, lres / batches);
+    printf("  batch pass, clip + setup + walk today %.1f instr; with the list %.1f (build %.1f per pass included)\n", today / batches,
+           listed / batches, CI_BUILD / ITEM_BATCHES);
+    printf("  all passes %.3f of today's instructions (today %.0f passes of %.1f)\n", (mixed - today + listed) / mixed, mpass, mixed / mpass);
+    free(pr); free(se); free(list);
+    return 0;
+  }
   if (getenv("PRIMARY_BATCH")) {
     /* Primary batches: per tile the camera segments in
      * path order in groups of 64 (one pool refill each: one tile at one
