@@ -1090,8 +1090,10 @@ __device__ __forceinline__ Rec make_rec(const View &sc, const DevObj &ob, V ow, 
     if (kind == kRectXY) { x = __builtin_fmaf(t, d.x, o.x); y = __builtin_fmaf(t, d.y, o.y); n = mk(0.f, 0.f, 1.f); }
     else if (kind == kRectXZ) { x = __builtin_fmaf(t, d.x, o.x); y = __builtin_fmaf(t, d.z, o.z); n = mk(0.f, 1.f, 0.f); }
     else { x = __builtin_fmaf(t, d.y, o.y); y = __builtin_fmaf(t, d.z, o.z); n = mk(1.f, 0.f, 0.f); }
-    r.u = (x - a0) / (a1 - a0);
-    r.v = (y - b0) / (b1 - b0);
+    if (need_uv) {  // (as the spheres: u = v = 0 where no texture reads them, rt_nw_debug_records' contract)
+      r.u = (x - a0) / (a1 - a0);
+      r.v = (y - b0) / (b1 - b0);
+    }
   }
   if (in.flags & 1) {
     p = rot_to_world(in, p);

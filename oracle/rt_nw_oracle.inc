@@ -588,8 +588,10 @@ static nw_rec nw_make_rec(const or_nw_scene *s, int32_t kk, const nw_obj *ob, NV
     if (kind == NW_XY) { x = fmaf(t, d.x, o.x); y = fmaf(t, d.y, o.y); n = nv(0.0f, 0.0f, 1.0f); }
     else if (kind == NW_XZ) { x = fmaf(t, d.x, o.x); y = fmaf(t, d.z, o.z); n = nv(0.0f, 1.0f, 0.0f); }
     else { x = fmaf(t, d.y, o.y); y = fmaf(t, d.z, o.z); n = nv(1.0f, 0.0f, 0.0f); }
-    r.u = (x - a0) / (a1 - a0);
-    r.v = (y - b0) / (b1 - b0);
+    if (need_uv) { /* as the spheres: u = v = 0 where no texture reads them */
+      r.u = (x - a0) / (a1 - a0);
+      r.v = (y - b0) / (b1 - b0);
+    }
   }
   if (in.flags & 1) {
     p = nw_rot_world(&in, p);

@@ -8,6 +8,11 @@ scene contents are pinned by an independent Python restatement of cuRAND's
 published generator plus the scene structure the reference code spells out;
 the GPU kernel is pinned bit-exactly to the oracle (tests/test_nw_gpu.py)
 and statistically to the reference's own render (gallery/final_scene_5000.png).
+The oracle itself, and the kernels directly, are held to an independent
+float64 model of the reference's semantics for every non-triangle kind —
+closest hits, hit records, textures, scatter relations, path colours, the
+statistics of media — in tests/test_nw_truth.py and tests/test_nw_truth_gpu.py
+(the model: tests/nw_truth.py).
 """
 import math
 import os
