@@ -41,10 +41,20 @@ template <bool F> __device__ __forceinline__ double madd(double a, double b, dou
 // v_div_scale / v_div_fmas / v_div_fixup), bit-identical to it for EVERY one
 // of the 2^32 inputs (rt_debug_exact_math checks all of them on the GPU:
 // tests/test_gpu_parity.py::test_exact_math_exhaustive).
-//  sqrt: the hardware v_sqrt_f32 (within 1 ulp), then the neighbour below or
-//  above when the exact residual x - s'*s says the true root lies past the
-//  midpoint (+inf passes through: its residuals are NaN); inputs below 2^-96
-//  keep the IEEE lowering.
+//  sqrt: y = v_rsq_f32(x), g = x * y (the root within ~2 ulp), then one
+//  Newton step on g with the exact residual d = fma(-g, g, x):
+//  fma(d, y / 2, g) is sqrt(x) to ~2^-46 relative before its one rounding,
+//  which with gfx950's v_rsq_f32 lands on the correctly rounded root for
+//  every input (with a 1-ulp v_rsq_f32 of another make it would miss a few
+//  inputs per binade, and a second Newton step on g and y / 2 would be due:
+//  the exhaustive test is what licenses the short form).  One transcendental
+//  and four multiplies / FMAs, no compare-and-select (the form before this
+//  one took v_sqrt_f32 and chose between it and its two neighbours by two
+//  residual signs: profiles/r10/exact_math/valu_forms.txt has both timed).
+//  Inputs outside [2^-96, inf) keep the IEEE lowering: zero, denormals
+//  (flushed by v_rsq_f32), negatives and NaN, whose residual would underflow
+//  or mean nothing, and +inf, where rsq(inf) * inf is NaN — one unsigned
+//  range test on the bit pattern.
 //  reciprocal: v_rcp_f32, then one Newton step with exact fma residual; the
 //  ranges where 1/x or x lies outside the normal range keep the IEEE
 //  division (a branch no realistic scene takes).
@@ -52,13 +62,11 @@ template <bool F> __device__ __forceinline__ double madd(double a, double b, dou
 // their ballot: the common path pays one compare and a scalar branch, not an
 // exec-mask save/restore — DESIGN.md §4.5.)
 __device__ __forceinline__ float sqrt_cr(float x) {
-  // below 2^-96 (zero, denormals — which v_sqrt_f32 flushes — negatives,
-  // NaN) the residuals would underflow: the IEEE lowering
-  const bool slow = !(x >= 0x1p-96f);
-  const float s = __builtin_amdgcn_sqrtf(x);
-  const float sm = __int_as_float(__float_as_int(s) - 1), sp = __int_as_float(__float_as_int(s) + 1);
-  float r = __builtin_fmaf(-sm, s, x) <= 0.0f ? sm : s;
-  r = __builtin_fmaf(-sp, s, x) > 0.0f ? sp : r;
+  // bits in [bits(2^-96), bits(+inf)): the sign bit and NaNs wrap above
+  const bool slow = __float_as_uint(x) - 0x0F800000u >= 0x7F800000u - 0x0F800000u;
+  const float y = __builtin_amdgcn_rsqf(x);
+  const float g = x * y, h = 0.5f * y;
+  float r = __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
   if (__builtin_expect(__ballot(slow) != 0, 0)) {
     if (slow) r = __builtin_sqrtf(x);
   }
