@@ -50,6 +50,15 @@ class RtNwFlat(C.Structure):
          ("background", C.c_float * 3)]
 
 
+class RtNwAdaptStats(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("stopped", C.c_int32), ("total_samples", C.c_int64), ("pixels_at_max", C.c_int64),
+                ("samples", C.c_int64), ("segments", C.c_int64),
+                ("active", C.POINTER(C.c_int64)), ("cap", C.c_int32), ("pad", C.c_int32)]
+
+
+NW_ADAPT_ON_PASS = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64)  # rt_nw_adapt_on_pass
+
+
 class RTError(RuntimeError):
     def __init__(self, what, code, msg):
         super().__init__(f"{what} failed: {ERRORS.get(code, code)}: {msg}")
@@ -202,6 +211,29 @@ SIGNATURES = {
     ),
     "rt_nw_accum_info": (C.c_int, [C.c_char_p, _ip, C.POINTER(C.c_uint64)]),
     "rt_nw_scene_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    # adaptive sampling of the Next-Week renderer
+    "rt_nw_adapt_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "rt_nw_adapt_pass": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 4 + [C.c_uint64] + [C.c_int32] * 3 + [C.POINTER(C.c_uint8), C.c_void_p],
+    ),
+    "rt_nw_adapt_export": (C.c_int, [C.c_void_p, _lp, C.POINTER(C.c_uint64), _ip, C.c_size_t]),
+    "rt_nw_adapt_import": (C.c_int, [C.c_void_p, _lp, C.POINTER(C.c_uint64), _ip, C.c_size_t]),
+    "rt_nw_adapt_resolve": (C.c_int, [C.c_void_p, C.c_void_p, _fp, C.c_void_p]),
+    "rt_nw_adapt_criterion": (
+        C.c_int,
+        [_lp, C.POINTER(C.c_uint64), _ip] + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_uint8), _dp, _lp],
+    ),
+    "rt_nw_render_adaptive": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 5 + [C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                                             C.c_uint64, C.c_char_p, C.c_double, _fp, _ip, _dp,
+                                                                             C.POINTER(RtNwAdaptStats), NW_ADAPT_ON_PASS,
+                                                                             C.c_void_p],
+    ),
+    "rt_nw_adapt_save": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 4 + [C.c_uint64]),
+    "rt_nw_adapt_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 6 + [C.c_uint64]),
+    "rt_nw_adapt_info": (C.c_int, [C.c_char_p, _ip, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

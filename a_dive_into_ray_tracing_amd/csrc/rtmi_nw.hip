@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <type_traits>
@@ -36,6 +38,17 @@ struct Args {
   // first sample of the launch (a progressive pass, rt_nw_render_pass; 0 in a plain render): item c of a tile
   // takes the samples s_base + c * chunk + [0, ns).  Wave-uniform: one scalar add per item.
   int32_t s_base;
+};
+
+// The adaptive form's work list (rt_nw_adapt_pass, DESIGN.md §9 "Adaptive sampling"): the pass's active tiles and,
+// per active tile, its pixel set as a mask (bit ly * 8 + lx); the samples each pixel holds (read, never written, by
+// the render kernels: adapt_advance_kernel adds the pass's count afterwards) and the second-moment sums.  Item
+// `it` renders tile tiles[it / nch]; Args' tiles is the list's length, s_base 0 and s_end the pass's sample count.
+struct AdaptArgs {
+  const int32_t *__restrict__ tiles;
+  const unsigned long long *__restrict__ masks;
+  const int32_t *__restrict__ n;     // [nrows][W]
+  unsigned long long *__restrict__ m2;  // [nrows][W]
 };
 
 // Two kernel shapes, the same per-path arithmetic (bit-identical images):
@@ -133,6 +146,13 @@ constexpr size_t kCuLds = 160 * 1024;
 constexpr size_t kPStaticLds = (sizeof(unsigned long long) * 3 * 64 * kPWaves + 23 * sizeof(float) + 255) / 256 * 256;
 constexpr size_t kPTwoBlockBudget = kCuLds / 2 - kPStaticLds;
 constexpr size_t kPLdsBudget = kCuLds - kPStaticLds;
+// ... of the adaptive kernels (ADAPT; rt_nw_adapt_pass): a wave's static LDS is four accumulators (the three colour
+// sums and the second moment) and its 64-entry pixel list, 2.25 KB against 1.5 KB, so their budgets are their own
+constexpr size_t kAdaptWaveLds = sizeof(unsigned long long) * 4 * 64 + sizeof(uint32_t) * 64;
+constexpr size_t kPStaticLdsA = (kAdaptWaveLds * kPWaves + 23 * sizeof(float) + 255) / 256 * 256;
+constexpr size_t kPTwoBlockBudgetA = kCuLds / 2 - kPStaticLdsA;
+constexpr size_t kPLdsBudgetA = kCuLds - kPStaticLdsA;
+constexpr size_t kLdsBudgetA = kLdsBudget - (kAdaptWaveLds - sizeof(unsigned long long) * 3 * 64) * kWaves;  // grid kernel: per block
 
 // RTMI_NW_PHASES builds (analysis only): wave-level cycles (s_memtime) of a
 // work item's loop passes: [0] closest hit, [1] hit record + texture +
@@ -214,22 +234,43 @@ __device__ __forceinline__ void stage_scene(const View &sc) {
 // One work item = (8x8 tile, <= chunk samples) on one wave: lanes pull
 // (pixel, sample) jobs from the item's queue and regenerate paths as theirs
 // end; sums in the wave's LDS accumulator, then one global add per pixel.
-template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
+// ADAPT (always CHUNKED; rt_nw_adapt_pass): the item's tile comes from the list of active tiles and its pixels
+// are the set bits of that tile's mask.  The lanes whose bit is set rank themselves and write pixel | n[pixel] <<
+// 8 into the wave's list (n < 2^20 fits); job q then goes to list entry q % nv (nv = the mask's popcount), sample
+// n[pixel] + s0 + q / nv, so pixels of one tile may start at different samples and a sparse tile's lanes take
+// several samples of one pixel side by side (nv * ns jobs: a tile with one active pixel runs ns lanes).  A path that ends also adds l^2, l = (fx + fy + fz) >> 18, to a
+// fourth accumulator (acc[3], flushed into ad.m2).  acc is indexed by the pixel's bit ly * 8 + lx here, by ly * vw
+// + lx otherwise.
+template <bool CHUNKED, bool LDS_NODES, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0, bool ADAPT = false>
 __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item, int lane,
-                                         unsigned long long (&acc)[3][64], unsigned long long *__restrict__ accum,
-                                         float *__restrict__ out, unsigned &nseg, const float *cl) {
-  const int tile = item / a.nch;
-  const int s0 = a.s_base + (item - tile * a.nch) * a.chunk;
+                                         unsigned long long (&acc)[ADAPT ? 4 : 3][64], unsigned long long *__restrict__ accum,
+                                         float *__restrict__ out, unsigned &nseg, const float *cl,
+                                         const AdaptArgs &ad = AdaptArgs{}, uint32_t *list = nullptr) {
+  static_assert(!ADAPT || CHUNKED, "the adaptive form adds into an accumulator");
+  const int slot = item / a.nch;  // the tile (ADAPT: its place in the list of active tiles)
+  const int tile = ADAPT ? ad.tiles[slot] : slot;
+  const int s0 = a.s_base + (item - slot * a.nch) * a.chunk;
   const int ns = min(a.chunk, a.s_end - s0);  // (the job decode below works on the item-local q < nv * ns)
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int x0 = tx * 8, y0 = ty * 8;
   const int vw = min(8, a.W - x0), vh = min(8, a.nrows_valid - y0);
-  const int nv = vw * vh;
+  const unsigned long long pmask = ADAPT ? ad.masks[slot] : 0ull;  // wave-uniform
+  const int nv = ADAPT ? int(__popcll(pmask)) : vw * vh;
   const int nq = nv * ns;
 
   acc[0][lane] = 0;
   acc[1][lane] = 0;
   acc[2][lane] = 0;
+  if constexpr (ADAPT) {
+    acc[3][lane] = 0;
+    if ((pmask >> lane) & 1ull) {  // (the host sets bits of the tile's valid pixels only)
+      const int rank = __builtin_amdgcn_mbcnt_hi(unsigned(pmask >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(pmask), 0u));
+      const size_t op = size_t(y0 + (lane >> 3)) * size_t(a.W) + size_t(x0 + (lane & 7));
+      list[rank] = uint32_t(lane) | uint32_t(ad.n[op]) << 8;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
 
   V o, d, T;
   float time = 0.f;
@@ -248,9 +289,19 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
   const uint32_t m_nv = 0x7FFFFFFFu / uint32_t(max(nv, 1)) + 1u, m_vw = 0x7FFFFFFFu / uint32_t(vw) + 1u;
   auto start = [&](int q) {
     const int qs = kMulDiv ? int(__umulhi(uint32_t(q) << 1, m_nv)) : q / nv;
-    const int s = s0 + qs;
-    const int px = q - qs * nv;
-    const int ly = kMulDiv ? int(__umulhi(uint32_t(px) << 1, m_vw)) : px / vw, lx = px - ly * vw;
+    int s = s0 + qs;
+    int px = q - qs * nv;
+    int ly, lx;
+    if constexpr (ADAPT) {  // the list entry: the pixel's bit and the samples it holds already
+      const uint32_t e = list[px];
+      px = int(e & 63u);
+      s += int(e >> 8);
+      ly = px >> 3;
+      lx = px & 7;
+    } else {
+      ly = kMulDiv ? int(__umulhi(uint32_t(px) << 1, m_vw)) : px / vw;
+      lx = px - ly * vw;
+    }
     const int i = x0 + lx;
     const int j = a.row0 + (y0 + ly) * a.row_step;
     rng.init(a.seed, uint64_t(j) * uint64_t(a.W) + uint64_t(i), uint32_t(s));
@@ -336,9 +387,18 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
     if (m) {
       if (done) {
         const int px = pxd >> 24;
-        atomicAdd(&acc[0][px], (unsigned long long)fixed(col.x));
-        atomicAdd(&acc[1][px], (unsigned long long)fixed(col.y));
-        atomicAdd(&acc[2][px], (unsigned long long)fixed(col.z));
+        if constexpr (ADAPT) {  // ... and the channel sum in units of 2^-14 (< 2^22), squared
+          const int64_t fx = fixed(col.x), fy = fixed(col.y), fz = fixed(col.z);
+          atomicAdd(&acc[0][px], (unsigned long long)fx);
+          atomicAdd(&acc[1][px], (unsigned long long)fy);
+          atomicAdd(&acc[2][px], (unsigned long long)fz);
+          const unsigned long long l = (unsigned long long)(fx + fy + fz) >> 18;
+          atomicAdd(&acc[3][px], l * l);
+        } else {  // (the statement form the existing kernels were compiled from: their code depends on it)
+          atomicAdd(&acc[0][px], (unsigned long long)fixed(col.x));
+          atomicAdd(&acc[1][px], (unsigned long long)fixed(col.y));
+          atomicAdd(&acc[2][px], (unsigned long long)fixed(col.z));
+        }
         const int rank = __builtin_amdgcn_mbcnt_hi(unsigned(m >> 32), __builtin_amdgcn_mbcnt_lo(unsigned(m), 0u));
         const int q = next + rank;
         if (q < nq) start(q);
@@ -365,7 +425,13 @@ __device__ __forceinline__ void run_item(const View &sc, const Args &a, int item
 #endif
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  if (lane < nv) {
+  if constexpr (ADAPT) {
+    if ((pmask >> lane) & 1ull) {
+      const size_t op = size_t(y0 + (lane >> 3)) * size_t(a.W) + size_t(x0 + (lane & 7));
+      for (int c = 0; c < 3; ++c) atomicAdd(&accum[op * 3 + c], acc[c][lane]);
+      atomicAdd(&ad.m2[op], acc[3][lane]);
+    }
+  } else if (lane < nv) {
     const int ly = lane / vw, lx = lane - ly * vw;
     const size_t o3 = (size_t(y0 + ly) * size_t(a.W) + size_t(x0 + lx)) * 3;
     for (int c = 0; c < 3; ++c) {
@@ -429,6 +495,72 @@ __global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU 
     run_item<CHUNKED, true, LDS_OBJS, GRID, S, TRI>(sc, a, int(it), lane, acc[wave], accum, out, nseg, cam_lds);
   }
   add_segments(nseg, lane, segments);
+}
+
+// The adaptive twins (rt_nw_adapt_pass): the same shapes with run_item's ADAPT form, kernels of their own so that
+// the ones above keep their code, registers and LDS.  Per wave four accumulators and the pixel list.
+template <bool LDS_NODES, bool LDS_OBJS, bool GRID, int TRI = 0>
+__global__ __launch_bounds__(64 * kWaves) void render_kernel_adapt(View sc, Args a, AdaptArgs ad,
+                                                                   unsigned long long *__restrict__ accum,
+                                                                   unsigned long long *__restrict__ segments) {
+  __shared__ unsigned long long acc[kWaves][4][64];
+  __shared__ uint32_t list[kWaves][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int item = blockIdx.x * kWaves + wave;
+  __shared__ float cam_lds[23];
+  stage_camera(cam_lds, a);
+  if constexpr (!LDS_NODES && !GRID) __syncthreads();  // (stage_scene's barrier covers the others)
+  stage_scene<LDS_NODES, LDS_OBJS, GRID>(sc);  // block barrier inside: before any wave leaves
+  if (item >= a.n_items) return;         // wave-uniform
+  unsigned nseg = 0;
+  run_item<true, LDS_NODES, LDS_OBJS, GRID, false, TRI, true>(sc, a, item, lane, acc[wave], accum, nullptr, nseg, cam_lds, ad, list[wave]);
+  add_segments(nseg, lane, segments);
+}
+
+template <bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
+__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI >= 4 ? affine_per_eu(TRI) : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent_adapt(View sc, Args a, AdaptArgs ad,
+                                                                  unsigned long long *__restrict__ accum,
+                                                                  unsigned long long *__restrict__ segments,
+                                                                  unsigned *__restrict__ counter) {
+  __shared__ unsigned long long acc[persist_waves<S>()][4][64];
+  __shared__ uint32_t list[persist_waves<S>()][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  __shared__ float cam_lds[23];
+  stage_camera(cam_lds, a);
+  stage_scene<true, LDS_OBJS, GRID>(sc);  // (its barrier covers the camera)
+  unsigned nseg = 0;
+  for (;;) {  // every wave leaves when the counter passes n_items
+    unsigned it = 0;
+    if (lane == 0) it = atomicAdd(counter, 1u);
+    it = __builtin_amdgcn_readfirstlane(__shfl(it, 0));
+    if (int(it) >= a.n_items) break;
+    run_item<true, true, LDS_OBJS, GRID, S, TRI, true>(sc, a, int(it), lane, acc[wave], accum, nullptr, nseg, cam_lds, ad, list[wave]);
+  }
+  add_segments(nseg, lane, segments);
+}
+
+// After an adaptive pass, on its stream: n[p] += s_count for the pass's active pixels (several items of a tile read
+// n during the pass, so the render kernel cannot advance it).  One 64-thread block per active tile.
+__global__ __launch_bounds__(64) void adapt_advance_kernel(const int32_t *__restrict__ tiles,
+                                                           const unsigned long long *__restrict__ masks, int32_t *__restrict__ n,
+                                                           int32_t W, int32_t tiles_x, int32_t s_count) {
+  const int tile = tiles[blockIdx.x];
+  const int lane = threadIdx.x;
+  if (!((masks[blockIdx.x] >> lane) & 1ull)) return;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  n[size_t(ty * 8 + (lane >> 3)) * size_t(W) + size_t(tx * 8 + (lane & 7))] += s_count;
+}
+
+// rt_nw_adapt_resolve: per-pixel means float(double(sum) * 2^-32 / n), 0 where n = 0
+__global__ void adapt_resolve_kernel(const unsigned long long *__restrict__ sum, const int32_t *__restrict__ n,
+                                     float *__restrict__ out, size_t npix) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= npix) return;
+  const int32_t k = n[i];
+  for (int c = 0; c < 3; ++c)
+    out[3 * i + c] = k > 0 ? float(double((long long)sum[3 * i + c]) * 0x1p-32 / double(k)) : 0.0f;
 }
 
 // Debug (parity investigations): the segments of ONE camera sample (pixel
@@ -718,6 +850,26 @@ struct rt_nw_ctx {
   unsigned long long *pass_accum = nullptr;
   size_t pass_cap = 0;
   int32_t pass_W = 0, pass_rows = 0, pass_spp = 0;
+  // adaptive sampling (rt_nw_adapt_*): a third accumulator, allocations of its own, adapt_W x adapt_rows pixels —
+  // the colour sums as pass_accum holds them, the second-moment sums and the samples each pixel holds.  n_host
+  // mirrors adapt_n (every change of n starts on the host), so a pass is checked against the 2^20 limit without a
+  // device read.  adapt_list: the work lists of the last two passes, used in turn — a pass uploads its list in
+  // stream order from the slot's host copy and waits only for the pass two back, which used the slot before.
+  unsigned long long *adapt_sum = nullptr, *adapt_m2 = nullptr;
+  int32_t *adapt_n = nullptr;
+  size_t adapt_cap = 0;  // pixels allocated
+  int32_t adapt_W = 0, adapt_rows = 0;
+  std::vector<int32_t> adapt_n_host;
+  struct AdaptList {
+    int32_t *tiles = nullptr;
+    unsigned long long *masks = nullptr;
+    size_t cap = 0;
+    std::vector<int32_t> host_tiles;  // (alive until the copy has run)
+    std::vector<unsigned long long> host_masks;
+    hipEvent_t done = nullptr;  // the end of the pass that used the slot
+    bool used = false;
+  } adapt_list[2];
+  int adapt_slot = 0;
   unsigned long long *segments = nullptr;
   unsigned *counter = nullptr;  // persistent kernel's work-item counter
   int32_t persist_blocks = 0;   // resident 16-wave blocks (CUs x blocks per CU), BVH kernels
@@ -851,8 +1003,12 @@ RTMI_EXPORT int rt_nw_ctx_destroy(rt_nw_ctx *ctx) {
   for (void *p : {(void *)ctx->obj, (void *)ctx->obj_id, (void *)ctx->med, (void *)ctx->med_id, (void *)ctx->inst, (void *)ctx->mat, (void *)ctx->tex,
                   (void *)ctx->pvec, (void *)ctx->pperm, (void *)ctx->img, (void *)ctx->imgd, (void *)ctx->nodes,
                   (void *)ctx->accum, (void *)ctx->scratch, (void *)ctx->segments, (void *)ctx->counter,
-                  (void *)ctx->grid_cells, (void *)ctx->grid_refs, (void *)ctx->grid_big, (void *)ctx->pass_accum})
+                  (void *)ctx->grid_cells, (void *)ctx->grid_refs, (void *)ctx->grid_big, (void *)ctx->pass_accum,
+                  (void *)ctx->adapt_sum, (void *)ctx->adapt_m2, (void *)ctx->adapt_n, (void *)ctx->adapt_list[0].tiles,
+                  (void *)ctx->adapt_list[0].masks, (void *)ctx->adapt_list[1].tiles, (void *)ctx->adapt_list[1].masks})
     if (p) (void)hipFree(p);
+  for (auto &l : ctx->adapt_list)
+    if (l.done) (void)hipEventDestroy(l.done);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
   delete ctx;
@@ -1173,9 +1329,16 @@ int check_rows_args(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t 
   return RT_OK;
 }
 
+// With adapt set (rt_nw_adapt_pass): pass_accum is the adaptive accumulator's sums, the work items cover the listed
+// tiles only, each active pixel p takes the samples n[p] + [0, spp), and the ADAPT twin of the same shape runs.
+struct AdaptLaunch {
+  AdaptArgs dev;    // the uploaded list and the accumulator's n and m2
+  int32_t n_tiles;  // active tiles
+};
+
 int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t spp, int32_t max_depth,
                      uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows, float *dev_strip, void *stream,
-                     int32_t s_base, unsigned long long *pass_accum, const char *who) {
+                     int32_t s_base, unsigned long long *pass_accum, const char *who, const AdaptLaunch *adapt = nullptr) {
   if (int rc = check_rows_args(ctx, cam, W, H, spp, max_depth, row0, row_step, nrows, s_base, pass_accum != nullptr, who)) return rc;
   if (!dev_strip && !pass_accum) return set_error(RT_EINVAL, "%s: null argument", who);
   const int32_t valid = std::min<int64_t>(nrows, (int64_t(H) - 1 - row0) / row_step + 1);
@@ -1195,13 +1358,18 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   a.row_step = row_step;
   a.nrows_valid = valid;
   a.tiles_x = (W + 7) / 8;
-  a.tiles = a.tiles_x * ((valid + 7) / 8);
+  a.tiles = adapt ? adapt->n_tiles : a.tiles_x * ((valid + 7) / 8);
+  // the adaptive kernels' static LDS is larger: staging budgets of their own
+  const size_t p_budget = adapt ? kPLdsBudgetA : kPLdsBudget, p_two_budget = adapt ? kPTwoBlockBudgetA : kPTwoBlockBudget,
+               g_budget = adapt ? kLdsBudgetA : kLdsBudget;
   // kernel shape: persistent when the nodes fit one CU's LDS budget, else grid
   const size_t node_bytes = size_t(ctx->nnodes) * 32, obj_bytes = size_t(ctx->nobj) * (sizeof(DevObj) + 4);
-  const bool use_grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
+  // (an adaptive pass of a grid that fits the plain kernels' budget but not its own walks the BVH: the same image)
+  const bool want_persist = RTMI_NW_PERSIST && ctx->persist_ok && ctx->persist_blocks_grid > 0;
+  const bool use_grid = accel_used(ctx) == RT_NW_ACCEL_GRID && (!adapt || grid_bytes(ctx) <= (want_persist ? p_budget : g_budget));
   const size_t gbytes = use_grid ? grid_bytes(ctx) : 0;
   const bool persist = RTMI_NW_PERSIST && ctx->persist_ok && (use_grid ? ctx->persist_blocks_grid > 0 : ctx->persist_blocks > 0) &&
-                       (use_grid || (ctx->nnodes > 0 && node_bytes <= kPLdsBudget));
+                       (use_grid || (ctx->nnodes > 0 && node_bytes <= p_budget));
   // the spheres-only instantiation of the persistent grid kernel
   const bool simple = persist && use_grid && ctx->simple && ctx->simple_ok && ctx->persist_blocks_simple > 0;
   const int32_t pblocks = simple ? ctx->persist_blocks_simple : use_grid ? ctx->persist_blocks_grid : ctx->persist_blocks;
@@ -1232,12 +1400,12 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8) ||
                          (ctx->has_tri == 5 && RTMI_NW_AFFINE_PER_EU < 8);
   const bool p_objs = RTMI_NW_LDS_OBJS && persist &&
-                      (node_bytes + obj_bytes <= kPTwoBlockBudget ||
-                       ((one_block || node_bytes > kPTwoBlockBudget) && node_bytes + obj_bytes <= kPLdsBudget));
-  const bool g_grid = use_grid && !persist && gbytes <= kLdsBudget;  // grid kernel with the grid staged per block
+                      (node_bytes + obj_bytes <= p_two_budget ||
+                       ((one_block || node_bytes > p_two_budget) && node_bytes + obj_bytes <= p_budget));
+  const bool g_grid = use_grid && !persist && gbytes <= g_budget;  // grid kernel with the grid staged per block
   if (use_grid && !persist && !g_grid) return set_error(RT_EINVAL, "rt_nw: grid does not fit the grid kernel's LDS");
-  const bool lds_nodes = !persist && !use_grid && ctx->nnodes > 0 && node_bytes <= kLdsBudget,
-             lds_objs = RTMI_NW_LDS_OBJS && lds_nodes && node_bytes + obj_bytes <= kLdsBudget;
+  const bool lds_nodes = !persist && !use_grid && ctx->nnodes > 0 && node_bytes <= g_budget,
+             lds_objs = RTMI_NW_LDS_OBJS && lds_nodes && node_bytes + obj_bytes <= g_budget;
   const size_t lds = use_grid ? gbytes
                      : persist ? (p_objs ? node_bytes + obj_bytes : node_bytes)
                                : lds_objs ? node_bytes + obj_bytes : lds_nodes ? node_bytes : 0;
@@ -1245,6 +1413,18 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   // (persistent) how many of its blocks stay resident with those bytes
   auto kernel_of = [&](auto tri) -> const void * {
     constexpr int T = decltype(tri)::value;
+    if (adapt) {  // the twin of the same shape
+      if constexpr (T < 3) {
+        if (simple) return (const void *)render_persistent_adapt<true, true, true>;
+        if (persist && use_grid) return (const void *)render_persistent_adapt<true, true, false, T>;
+        if (g_grid) return (const void *)render_kernel_adapt<false, false, true, T>;
+      }
+      return persist && p_objs ? (const void *)render_persistent_adapt<true, false, false, T>
+             : persist         ? (const void *)render_persistent_adapt<false, false, false, T>
+             : lds_objs        ? (const void *)render_kernel_adapt<true, true, false, T>
+             : lds_nodes       ? (const void *)render_kernel_adapt<true, false, false, T>
+                               : (const void *)render_kernel_adapt<false, false, false, T>;
+    }
     if constexpr (T >= 3)  // (BVH shapes only)
       return persist && p_objs ? (const void *)render_persistent<true, true, false, false, T>
              : persist         ? (const void *)render_persistent<true, false, false, false, T>
@@ -1318,6 +1498,36 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   auto launch_t = [&](auto chunked, auto tri) {
     constexpr bool C = decltype(chunked)::value;
     constexpr int T = decltype(tri)::value;
+    if constexpr (C) {
+      if (adapt) {
+        const AdaptArgs &ad = adapt->dev;
+        if constexpr (T < 3) {
+          if (simple) {
+            hipLaunchKernelGGL((render_persistent_adapt<true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
+            return;
+          }
+          if (persist && use_grid) {
+            hipLaunchKernelGGL((render_persistent_adapt<true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
+            return;
+          }
+          if (!persist && g_grid) {
+            hipLaunchKernelGGL((render_kernel_adapt<false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
+            return;
+          }
+        }
+        if (persist && p_objs)
+          hipLaunchKernelGGL((render_persistent_adapt<true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
+        else if (persist)
+          hipLaunchKernelGGL((render_persistent_adapt<false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
+        else if (lds_objs)
+          hipLaunchKernelGGL((render_kernel_adapt<true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
+        else if (lds_nodes)
+          hipLaunchKernelGGL((render_kernel_adapt<true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
+        else
+          hipLaunchKernelGGL((render_kernel_adapt<false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ad, acc_buf, ctx->segments);
+        return;
+      }
+    }
     if constexpr (T < 3) {  // (a scene with placements has no grid)
       if (simple) {
         hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
@@ -1542,6 +1752,340 @@ RTMI_EXPORT int rt_nw_accum_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *
   if (int rc = rt_nw_accum_reset(ctx, W, nrows)) return rc;
   if (int rc = rt_nw_accum_import(ctx, raw.data(), raw.size(), h.spp_done)) return rc;
   *spp_done = h.spp_done;
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// adaptive sampling (DESIGN.md §9 "Adaptive sampling")
+// ---------------------------------------------------------------------------
+// The adaptive accumulator holds, per pixel, the fixed-point colour sums, the sum of l^2 and the number n of samples
+// behind them.  A pass gives every active pixel p the samples [n[p], n[p] + s_count): a sample's contribution
+// depends on (seed, pixel, sample index) alone, so p's sums are those of a plain render of n[p] samples at p,
+// whatever its neighbours received.
+namespace {
+constexpr int32_t kAdaptMaxSpp = 1 << 20;  // RT_NW_ADAPT_MAX_SPP: 192^2 * 2^28 * 2^20 < 2^64 keeps m2 from overflowing
+
+size_t adapt_pixels(const rt_nw_ctx *c) { return size_t(c->adapt_W) * size_t(c->adapt_rows); }
+
+int adapt_wait(rt_nw_ctx *ctx) {  // nothing of the context still running
+  if (ctx->last_stream) HIP_TRY(hipStreamSynchronize(ctx->last_stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_adapt_reset(rt_nw_ctx *ctx, int32_t W, int32_t nrows) {
+  if (!ctx) return set_error(RT_EINVAL, "null ctx");
+  if (W < 1 || nrows < 1 || int64_t(W) * nrows >= (int64_t(1) << 40))
+    return set_error(RT_EINVAL, "rt_nw_adapt_reset: bad size %dx%d", W, nrows);
+  Guard g(ctx->device);
+  const size_t n = size_t(W) * size_t(nrows);
+  if (int rc = adapt_wait(ctx)) return rc;
+  if (ctx->adapt_cap < n) {
+    ctx->adapt_cap = 0;
+    ctx->adapt_W = ctx->adapt_rows = 0;
+    int rc;
+    if ((rc = alloc_copy<unsigned long long>(&ctx->adapt_sum, nullptr, n * 3)) ||
+        (rc = alloc_copy<unsigned long long>(&ctx->adapt_m2, nullptr, n)) || (rc = alloc_copy<int32_t>(&ctx->adapt_n, nullptr, n)))
+      return rc;
+    ctx->adapt_cap = n;
+  }
+  ctx->adapt_W = W;
+  ctx->adapt_rows = nrows;
+  ctx->adapt_n_host.assign(n, 0);
+  HIP_TRY(hipMemsetAsync(ctx->adapt_sum, 0, n * 3 * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->adapt_m2, 0, n * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->adapt_n, 0, n * sizeof(int32_t), ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_adapt_pass(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t s_count,
+                                 int32_t max_depth, uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows,
+                                 const uint8_t *active, void *stream) {
+  const char *who = "rt_nw_adapt_pass";
+  if (!ctx || !cam) return set_error(RT_EINVAL, "%s: null argument", who);
+  if (s_count < 0 || s_count > kAdaptMaxSpp)
+    return set_error(RT_EINVAL, "%s: bad sample count %d (a pixel holds at most 2^20 samples)", who, s_count);
+  if (!ctx->adapt_sum || !ctx->adapt_W || W != ctx->adapt_W || nrows != ctx->adapt_rows)
+    return set_error(RT_EINVAL, "%s: accumulator is not %dx%d (call rt_nw_adapt_reset)", who, W, nrows);
+  if (adapt_pixels(ctx) > ctx->adapt_cap || ctx->adapt_n_host.size() != adapt_pixels(ctx))
+    return set_error(RT_EHIP, "internal: adaptive accumulator too small");
+  if (int rc = check_rows_args(ctx, cam, W, H, std::max(s_count, 1), max_depth, row0, row_step, nrows, 0, true, who)) return rc;
+  // the work list: per tile with an active pixel inside the image, the mask of those pixels (bit ly * 8 + lx)
+  const int32_t valid = std::min<int64_t>(nrows, (int64_t(H) - 1 - row0) / row_step + 1);
+  const int32_t tiles_x = (W + 7) / 8, tiles_y = (valid + 7) / 8;
+  std::vector<int32_t> tiles;
+  std::vector<unsigned long long> masks;
+  if (s_count > 0) {
+    for (int32_t ty = 0; ty < tiles_y; ++ty)
+      for (int32_t tx = 0; tx < tiles_x; ++tx) {
+        unsigned long long m = 0;
+        const int32_t vh = std::min(8, valid - ty * 8), vw = std::min(8, W - tx * 8);
+        for (int32_t ly = 0; ly < vh; ++ly)
+          for (int32_t lx = 0; lx < vw; ++lx) {
+            const size_t p = size_t(ty * 8 + ly) * size_t(W) + size_t(tx * 8 + lx);
+            if (active && !active[p]) continue;
+            if (ctx->adapt_n_host[p] > kAdaptMaxSpp - s_count)
+              return set_error(RT_EINVAL, "%s: pixel (%d, row %d) holds %d samples: %d more would pass 2^20", who, tx * 8 + lx,
+                               ty * 8 + ly, ctx->adapt_n_host[p], s_count);
+            m |= 1ull << (ly * 8 + lx);
+          }
+        if (m) {
+          tiles.push_back(ty * tiles_x + tx);
+          masks.push_back(m);
+        }
+      }
+  }
+  Guard g(ctx->device);
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (tiles.empty()) {  // nothing to sample: no launch, a count of zero segments
+    if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
+    ctx->last_stream = st;
+    HIP_TRY(hipMemsetAsync(ctx->segments, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipEventRecord(ctx->last_done, st));
+    return RT_OK;
+  }
+  // the list goes into the slot the pass before the last one used (that pass has to have ended: the host waits for
+  // it alone), uploaded in stream order from the slot's host copy; the pass is asynchronous on `stream`
+  rt_nw_ctx::AdaptList &L = ctx->adapt_list[ctx->adapt_slot];
+  ctx->adapt_slot ^= 1;
+  if (!L.done) HIP_TRY(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+  if (L.used) HIP_TRY(hipEventSynchronize(L.done));
+  L.used = false;
+  const size_t nt = tiles.size();
+  if (nt > L.cap) {
+    L.cap = 0;
+    int rc;
+    if ((rc = alloc_copy<int32_t>(&L.tiles, nullptr, nt)) || (rc = alloc_copy<unsigned long long>(&L.masks, nullptr, nt))) return rc;
+    L.cap = nt;
+  }
+  L.host_tiles.swap(tiles);
+  L.host_masks.swap(masks);
+  const std::vector<int32_t> &tiles_h = L.host_tiles;
+  const std::vector<unsigned long long> &masks_h = L.host_masks;
+  // (recorded whatever follows, so that the slot is not handed out again while a copy or the pass may still run)
+  struct MarkSlot {
+    rt_nw_ctx::AdaptList &l;
+    hipStream_t s;
+    ~MarkSlot() { l.used = hipEventRecord(l.done, s) == hipSuccess; }
+  } mark_slot{L, st};
+  HIP_TRY(hipMemcpyAsync(L.tiles, tiles_h.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(L.masks, masks_h.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+  AdaptLaunch al;
+  al.dev.tiles = L.tiles;
+  al.dev.masks = L.masks;
+  al.dev.n = ctx->adapt_n;
+  al.dev.m2 = ctx->adapt_m2;
+  al.n_tiles = int32_t(nt);
+  if (int rc = render_rows_impl(ctx, cam, W, H, s_count, max_depth, seed, row0, row_step, nrows, nullptr, stream, 0,
+                                ctx->adapt_sum, who, &al))
+    return rc;
+  hipLaunchKernelGGL(adapt_advance_kernel, dim3(unsigned(nt)), dim3(64), 0, st, L.tiles, L.masks, ctx->adapt_n, W, tiles_x,
+                     s_count);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->last_done, st));  // (the pass ends with the counts)
+  for (size_t k = 0; k < nt; ++k) {
+    const int32_t ty = tiles_h[k] / tiles_x, tx = tiles_h[k] - ty * tiles_x;
+    for (int b = 0; b < 64; ++b)
+      if ((masks_h[k] >> b) & 1ull) ctx->adapt_n_host[size_t(ty * 8 + (b >> 3)) * size_t(W) + size_t(tx * 8 + (b & 7))] += s_count;
+  }
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_adapt_export(rt_nw_ctx *ctx, int64_t *sum, uint64_t *m2, int32_t *n, size_t npix) {
+  if (!ctx || !sum || !m2 || !n) return set_error(RT_EINVAL, "rt_nw_adapt_export: null argument");
+  const size_t want = adapt_pixels(ctx);
+  if (!ctx->adapt_sum || !want || npix != want)
+    return set_error(RT_EINVAL, "rt_nw_adapt_export: %zu pixels, accumulator %zu (rt_nw_adapt_reset)", npix, want);
+  Guard g(ctx->device);
+  HIP_TRY(hipStreamSynchronize(ctx->last_stream ? ctx->last_stream : ctx->stream));
+  HIP_TRY(hipMemcpy(sum, ctx->adapt_sum, npix * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(m2, ctx->adapt_m2, npix * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n, ctx->adapt_n, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_adapt_import(rt_nw_ctx *ctx, const int64_t *sum, const uint64_t *m2, const int32_t *n, size_t npix) {
+  if (!ctx || !sum || !m2 || !n) return set_error(RT_EINVAL, "rt_nw_adapt_import: null argument");
+  const size_t want = adapt_pixels(ctx);
+  if (!ctx->adapt_sum || !want || npix != want)
+    return set_error(RT_EINVAL, "rt_nw_adapt_import: %zu pixels, accumulator %zu (call rt_nw_adapt_reset)", npix, want);
+  for (size_t p = 0; p < npix; ++p)
+    if (n[p] < 0 || n[p] > kAdaptMaxSpp) return set_error(RT_EINVAL, "rt_nw_adapt_import: sample count outside [0, 2^20]");
+  Guard g(ctx->device);
+  if (int rc = adapt_wait(ctx)) return rc;
+  HIP_TRY(hipMemcpy(ctx->adapt_sum, sum, npix * 3 * sizeof(int64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->adapt_m2, m2, npix * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->adapt_n, n, npix * sizeof(int32_t), hipMemcpyHostToDevice));
+  ctx->adapt_n_host.assign(n, n + npix);
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_adapt_resolve(rt_nw_ctx *ctx, float *dev_mean, float *host_mean, void *stream) {
+  if (!ctx) return set_error(RT_EINVAL, "null ctx");
+  if (!ctx->adapt_sum || !ctx->adapt_W) return set_error(RT_EINVAL, "rt_nw_adapt_resolve: no accumulator (rt_nw_adapt_reset)");
+  if (!dev_mean && !host_mean) return set_error(RT_EINVAL, "rt_nw_adapt_resolve: no output");
+  Guard g(ctx->device);
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const size_t npix = adapt_pixels(ctx), n = npix * 3;
+  float *out = dev_mean;
+  if (!out) {  // through the context's float scratch, which renders share
+    if (n > ctx->scratch_cap) {
+      if (int rc = adapt_wait(ctx)) return rc;
+      ctx->scratch_cap = 0;
+      if (int rc = alloc_copy<float>(&ctx->scratch, nullptr, n)) return rc;
+      ctx->scratch_cap = n;
+    }
+    out = ctx->scratch;
+  }
+  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
+  ctx->last_stream = st;
+  hipLaunchKernelGGL(adapt_resolve_kernel, dim3(unsigned((npix + 255) / 256)), dim3(256), 0, st, ctx->adapt_sum, ctx->adapt_n, out,
+                     npix);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && host_mean) e = hipMemcpyAsync(host_mean, out, n * sizeof(float), hipMemcpyDeviceToHost, st);
+  (void)hipEventRecord(ctx->last_done, st);
+  if (e == hipSuccess && host_mean) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_adapt_resolve: %s", hipGetErrorString(e));
+  return RT_OK;
+}
+
+namespace {
+int adapt_header(rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t row0, int32_t row_step, int32_t nrows,
+                 int32_t max_depth, uint64_t seed, CkptHeader &h) {
+  h = CkptHeader{};
+  if (int rc = rt_nw_scene_hash(scene, &h.scene_hash)) return rc;
+  h.W = W;
+  h.H = H;
+  h.row0 = row0;
+  h.row_step = row_step;
+  h.nrows = nrows;
+  h.max_depth = max_depth;
+  h.seed = seed;
+  h.camera_hash = camera_hash(cam);
+  return RT_OK;
+}
+}  // namespace
+
+RTMI_EXPORT int rt_nw_adapt_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t H,
+                                 int32_t row0, int32_t row_step, int32_t max_depth, uint64_t seed) {
+  if (!ctx || !path || !scene || !cam) return set_error(RT_EINVAL, "rt_nw_adapt_save: null argument");
+  if (!ctx->adapt_sum || !ctx->adapt_W) return set_error(RT_EINVAL, "rt_nw_adapt_save: no accumulator (rt_nw_adapt_reset)");
+  CkptHeader h;
+  if (int rc = adapt_header(scene, cam, ctx->adapt_W, H, row0, row_step, ctx->adapt_rows, max_depth, seed, h)) return rc;
+  const size_t npix = adapt_pixels(ctx);
+  std::vector<int64_t> sum(npix * 3);
+  std::vector<uint64_t> m2(npix);
+  std::vector<int32_t> n(npix);
+  if (int rc = rt_nw_adapt_export(ctx, sum.data(), m2.data(), n.data(), npix)) return rc;
+  h.spp_done = *std::max_element(n.begin(), n.end());  // the largest count a pixel holds
+  return adapt_ckpt_write(path, h, sum.data(), m2.data(), n.data());
+}
+
+RTMI_EXPORT int rt_nw_adapt_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W,
+                                 int32_t H, int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed) {
+  if (!ctx || !path || !scene || !cam) return set_error(RT_EINVAL, "rt_nw_adapt_load: null argument");
+  if (W < 1 || nrows < 1) return set_error(RT_EINVAL, "rt_nw_adapt_load: bad size %dx%d", W, nrows);
+  CkptHeader want, h{};
+  if (int rc = adapt_header(scene, cam, W, H, row0, row_step, nrows, max_depth, seed, want)) return rc;
+  if (int rc = adapt_ckpt_read(path, h, nullptr, nullptr, nullptr)) return rc;
+  if (h.W != W || h.H != H || h.row0 != row0 || h.row_step != row_step || h.nrows != nrows || h.max_depth != max_depth ||
+      h.seed != seed || h.scene_hash != want.scene_hash || h.camera_hash != want.camera_hash)
+    return set_error(RT_EINVAL, "rt_nw_adapt_load: %s was made for another render (size, rows, depth, seed, scene or camera)",
+                     path);
+  std::vector<int64_t> sum;
+  std::vector<uint64_t> m2;
+  std::vector<int32_t> n;
+  if (int rc = adapt_ckpt_read(path, h, &sum, &m2, &n)) return rc;  // (the header matches this render: W * nrows pixels)
+  for (int32_t v : n)
+    if (v < 0 || v > kAdaptMaxSpp) return set_error(RT_EIO, "rt_nw_adapt_load: %s holds a bad sample count", path);
+  if (int rc = rt_nw_adapt_reset(ctx, W, nrows)) return rc;
+  return rt_nw_adapt_import(ctx, sum.data(), m2.data(), n.data(), n.size());
+}
+
+// The driver: pass, export, criterion, next mask, until nothing is active or the time limit passes.  The criterion
+// runs on the host (rt_nw_adapt_criterion): the export of a W x nrows strip is small beside a pass.
+RTMI_EXPORT int rt_nw_render_adaptive(rt_nw_ctx *ctx, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
+                                      int32_t min_spp, int32_t max_spp, int32_t pass_spp, double threshold, double floor,
+                                      int32_t dilate, int32_t max_depth, uint64_t seed, const char *checkpoint, double time_limit,
+                                      float *mean_out, int32_t *n_out, double *err_out, rt_nw_adapt_stats *stats,
+                                      rt_nw_adapt_on_pass on_pass, void *user) {
+  const char *who = "rt_nw_render_adaptive";
+  if (!ctx || !cam) return set_error(RT_EINVAL, "%s: null argument", who);
+  if (checkpoint && !scene) return set_error(RT_EINVAL, "%s: a checkpoint needs the scene (its hash)", who);
+  if (pass_spp < 1) return set_error(RT_EINVAL, "%s: pass_spp must be at least 1", who);
+  if (W < 1 || H < 1 || int64_t(W) * H >= (int64_t(1) << 40)) return set_error(RT_EINVAL, "%s: bad size", who);
+  const size_t npix = size_t(W) * size_t(H);
+  std::vector<int64_t> sum(npix * 3);
+  std::vector<uint64_t> m2(npix);
+  std::vector<int32_t> n(npix);
+  std::vector<uint8_t> active(npix);
+  std::vector<double> err(npix);
+  int64_t n_active = 0;
+  // (the criterion's own checks of min_spp, max_spp, threshold, floor and dilate come first)
+  if (int rc = rt_nw_adapt_criterion(sum.data(), m2.data(), n.data(), W, H, min_spp, max_spp, threshold, floor, dilate,
+                                     active.data(), err.data(), &n_active))
+    return rc;
+  bool resumed = false;
+  if (checkpoint) {
+    if (FILE *probe = std::fopen(checkpoint, "rb")) {
+      std::fclose(probe);
+      if (int rc = rt_nw_adapt_load(ctx, checkpoint, scene, cam, W, H, 0, 1, H, max_depth, seed)) return rc;
+      resumed = true;
+    }
+  }
+  if (!resumed)
+    if (int rc = rt_nw_adapt_reset(ctx, W, H)) return rc;
+  if (stats) {
+    stats->passes = 0;
+    stats->stopped = 0;
+    stats->total_samples = stats->pixels_at_max = stats->samples = stats->segments = 0;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int32_t pass = 0;; ++pass) {
+    if (int rc = rt_nw_adapt_export(ctx, sum.data(), m2.data(), n.data(), npix)) return rc;
+    if (int rc = rt_nw_adapt_criterion(sum.data(), m2.data(), n.data(), W, H, min_spp, max_spp, threshold, floor, dilate,
+                                       active.data(), err.data(), &n_active))
+      return rc;
+    if (n_active == 0) break;
+    if (pass > 0 && time_limit >= 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= time_limit) {
+      if (stats) stats->stopped = 1;  // (at least one pass always runs)
+      break;
+    }
+    int32_t top = 0;  // no active pixel passes max_spp
+    for (size_t p = 0; p < npix; ++p)
+      if (active[p]) top = std::max(top, n[p]);
+    const int32_t k = std::min(pass_spp, max_spp - top);
+    if (int rc = rt_nw_adapt_pass(ctx, cam, W, H, k, max_depth, seed, 0, 1, H, active.data(), nullptr)) return rc;
+    if (stats) {
+      if (stats->active && pass < stats->cap) stats->active[pass] = n_active;
+      stats->passes = pass + 1;
+      uint64_t segs = 0;  // (waits for the pass, as the next export would)
+      if (int rc = rt_nw_ctx_last_segments(ctx, &segs)) return rc;
+      stats->segments += int64_t(segs);
+      for (size_t p = 0; p < npix; ++p) stats->samples += active[p] ? k : 0;
+    }
+    if (checkpoint)  // (waits for the pass)
+      if (int rc = rt_nw_adapt_save(ctx, checkpoint, scene, cam, H, 0, 1, max_depth, seed)) return rc;
+    if (on_pass && on_pass(user, pass + 1, n_active)) {  // the caller ends the run: the state so far is returned
+      if (stats) stats->stopped = 2;
+      if (int rc = rt_nw_adapt_export(ctx, sum.data(), m2.data(), n.data(), npix)) return rc;
+      if (int rc = rt_nw_adapt_criterion(sum.data(), m2.data(), n.data(), W, H, min_spp, max_spp, threshold, floor, dilate,
+                                         active.data(), err.data(), &n_active))
+        return rc;
+      break;
+    }
+  }
+  if (stats)
+    for (size_t p = 0; p < npix; ++p) {
+      stats->total_samples += n[p];
+      stats->pixels_at_max += n[p] >= max_spp ? 1 : 0;
+    }
+  if (n_out) std::memcpy(n_out, n.data(), npix * sizeof(int32_t));
+  if (err_out) std::memcpy(err_out, err.data(), npix * sizeof(double));
+  if (mean_out)
+    if (int rc = rt_nw_adapt_resolve(ctx, nullptr, mean_out, nullptr)) return rc;
   return RT_OK;
 }
 

@@ -10,6 +10,16 @@
 //   rtmi_nw_render --obj FILE.obj [--obj-mat lambertian|metal|glass] [--obj-smooth] [--obj-gen-normals]
 //                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble] [--width W] ...
 //   either form: [--shutter T0,T1] [--pass-spp N] [--checkpoint FILE] [--time-limit SECONDS] [--pfm FILE]
+//                [--adaptive THRESHOLD [--min-spp N] [--spp-map FILE.pfm]]
+//
+// --adaptive THRESHOLD samples every pixel until the relative standard error of
+// its mean (rt_nw_adapt_criterion, floor 0.03, dilation 1) is at most THRESHOLD
+// (rt_nw_render_adaptive): at least --min-spp samples (default 16), at most
+// --spp, in passes of --pass-spp (default kDefaultAdaptPassSpp) over the pixels
+// still active.  --checkpoint (an adaptive checkpoint, rt_nw_adapt_save),
+// --time-limit, --out and --pfm work as above; --spp-map FILE.pfm writes the
+// per-pixel sample counts (the count in all three channels).  stderr carries
+// the total samples and the share of pixels at the maximum.
 //
 // --pass-spp N renders in passes of N samples (rt_nw_render_pass), each a
 // bounded kernel launch; the image is bit for bit the one of a single render of
@@ -61,6 +71,10 @@
 // 5 120-triangle mesh -0.1 / +5.5 / +25 / +121 % — a small pass gives the persistent kernels few, short work
 // items.  1024 is free and still a pass of about a second on those scenes.
 static const int kDefaultPassSpp = 1024;
+// Default --pass-spp under --adaptive: the criterion is looked at after every pass, so a pass is the grain of the
+// sample-count map; late passes hold few tiles and their work items shrink with them (the chunk rule takes the
+// active tile count).
+static const int kDefaultAdaptPassSpp = 64;
 
 static int die(const char *what, int rc) {
   std::fprintf(stderr, "rtmi_nw_render: %s failed (%d): %s\n", what, rc, rt_last_error());
@@ -98,9 +112,10 @@ static bool read_p6(const char *path, std::vector<uint8_t> &px, int &w, int &h) 
 }
 
 int main(int argc, char **argv) {
-  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture, checkpoint, pfm;
-  int pass_spp = 0;
-  double time_limit = -1;
+  std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture, checkpoint, pfm, spp_map;
+  int pass_spp = 0, min_spp = 16;
+  double time_limit = -1, adaptive = -1;
+  bool min_given = false;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
   bool copies_given = false, move_given = false, shutter_given = false, tumble = false;
@@ -151,6 +166,11 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--pass-spp")) pass_spp = std::atoi(need("--pass-spp"));
     else if (!std::strcmp(argv[a], "--checkpoint")) checkpoint = need("--checkpoint");
     else if (!std::strcmp(argv[a], "--pfm")) pfm = need("--pfm");
+    else if (!std::strcmp(argv[a], "--spp-map")) spp_map = need("--spp-map");
+    else if (!std::strcmp(argv[a], "--min-spp")) { min_spp = std::atoi(need("--min-spp")); min_given = true; }
+    else if (!std::strcmp(argv[a], "--adaptive")) {
+      if (!numbers(need("--adaptive"), &adaptive, 1) || adaptive < 0) { std::fprintf(stderr, "--adaptive takes THRESHOLD >= 0\n"); return 2; }
+    }
     else if (!std::strcmp(argv[a], "--time-limit")) {
       if (!numbers(need("--time-limit"), &time_limit, 1) || time_limit < 0) { std::fprintf(stderr, "--time-limit takes SECONDS >= 0\n"); return 2; }
     }
@@ -169,6 +189,10 @@ int main(int argc, char **argv) {
                            "         %d samples.  Measured cost of splitting 1024 spp at 800 x 800 into passes of 1024 / 256 / 64 /\n"
                            "         16 samples: final scene -0.2 / +14 / +42 / +175 %%, a 4 x 4 mesh field -0.1 / +5.5 / +25 / +121 %%\n"
                            "  --pfm FILE: the mean image as floats\n"
+                           "  --adaptive THRESHOLD [--min-spp N] [--spp-map FILE.pfm]: sample each pixel until the relative standard\n"
+                           "         error of its mean is at most THRESHOLD, between --min-spp (default 16) and --spp samples, in\n"
+                           "         passes of --pass-spp (default %d) over the pixels still active; --checkpoint, --time-limit,\n"
+                           "         --out and --pfm as above; --spp-map: the per-pixel sample counts as a PFM\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
                            "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
@@ -180,7 +204,7 @@ int main(int argc, char **argv) {
                            "         times [0, 1] (motion blur under the default shutter)\n"
                            "  --obj-tumble (needs --obj): every copy as an affine placement of the shared mesh, scaled by\n"
                            "         0.75 + 0.25 sin(2.9 q), turned 37 q degrees about a skew axis and stood on the ground\n",
-                   argv[0], argv[0], kDefaultPassSpp);
+                   argv[0], argv[0], kDefaultPassSpp, kDefaultAdaptPassSpp);
       return 2;
     }
   }
@@ -212,6 +236,9 @@ int main(int argc, char **argv) {
   if (!obj.empty()) which = 0;
   if (H < 0) H = W;  // aspect_ratio = 1.0, main.cu:517-519
   if (pass_spp < 0) { std::fprintf(stderr, "--pass-spp takes a count >= 1\n"); return 2; }
+  if (adaptive < 0 && (min_given || !spp_map.empty())) { std::fprintf(stderr, "--min-spp and --spp-map need --adaptive\n"); return 2; }
+  if (adaptive >= 0 && pass_spp == 0) pass_spp = kDefaultAdaptPassSpp;
+  if (adaptive >= 0 && (min_spp < 0 || min_spp > spp || spp < 2)) { std::fprintf(stderr, "--adaptive needs 0 <= --min-spp <= --spp and --spp >= 2\n"); return 2; }
   if (pass_spp == 0 && (!checkpoint.empty() || time_limit >= 0)) pass_spp = kDefaultPassSpp;
   if (pass_spp > 0 && spp < 1) { std::fprintf(stderr, "--spp takes a count >= 1\n"); return 2; }
   std::vector<uint8_t> img;
@@ -268,7 +295,24 @@ int main(int argc, char **argv) {
   const auto t0 = std::chrono::steady_clock::now();
   uint64_t segs = 0;
   int spp_resumed = 0;
-  if (pass_spp > 0) {
+  int div = 0;              // what the sums are divided by for the image: spp, or 1 where sum holds means (--adaptive)
+  double rendered = -1;     // samples this run rendered
+  std::vector<int32_t> counts;
+  if (adaptive >= 0) {
+    counts.resize(size_t(W) * H);
+    rt_nw_adapt_stats st{};
+    if ((rc = rt_nw_render_adaptive(ctx, s, &cam, W, H, min_spp, spp, pass_spp, adaptive, 0.03, 1, depth, seed,
+                                    checkpoint.empty() ? nullptr : checkpoint.c_str(), time_limit, sum.data(), counts.data(), nullptr, &st, nullptr, nullptr)))
+      return die("rt_nw_render_adaptive", rc);
+    std::fprintf(stderr, "{\"adaptive\": %g, \"passes\": %d, \"stopped_by_time_limit\": %d, \"total_samples\": %lld, "
+                         "\"mean_spp\": %.3f, \"share_at_max\": %.4f}\n",
+                 adaptive, st.passes, st.stopped, (long long)st.total_samples, double(st.total_samples) / (double(W) * H),
+                 double(st.pixels_at_max) / (double(W) * H));
+    div = 1;  // (sum holds the per-pixel means; "spp" below stays the maximum)
+    rendered = double(st.samples);
+    segs = uint64_t(st.segments);
+    if (st.passes == 0) rendered = 0;  // (a finished checkpoint: nothing was rendered)
+  } else if (pass_spp > 0) {
     if ((rc = rt_nw_accum_reset(ctx, W, H))) return die("rt_nw_accum_reset", rc);
     int done = 0;
     if (!checkpoint.empty()) {
@@ -299,7 +343,8 @@ int main(int argc, char **argv) {
     rt_nw_ctx_last_segments(ctx, &segs);
   }
   const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const double rendered = double(W) * H * std::max(spp - spp_resumed, 0);
+  if (!div) div = spp;
+  if (rendered < 0) rendered = double(W) * H * std::max(spp - spp_resumed, 0);
   std::fprintf(stderr,
                "{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"seconds\": %.6f, "
                "\"msamples_per_s\": %.3f, \"segments_per_sample\": %.4f}\n",
@@ -314,7 +359,7 @@ int main(int argc, char **argv) {
     for (int i = 0; i < W; i++) {
       int v[3];
       for (int c = 0; c < 3; c++) {
-        const float mean = sum[(size_t(j) * W + i) * 3 + c] / float(spp);
+        const float mean = sum[(size_t(j) * W + i) * 3 + c] / float(div);
         v[c] = int(255.99 * double(std::sqrt(mean)));
       }
       if (p6) {
@@ -324,6 +369,11 @@ int main(int argc, char **argv) {
       }
     }
   if (f != stdout) std::fclose(f);
-  if (!pfm.empty() && (rc = rt_write_pfm(pfm.c_str(), sum.data(), W, H, spp))) return die("rt_write_pfm", rc);
+  if (!pfm.empty() && (rc = rt_write_pfm(pfm.c_str(), sum.data(), W, H, div))) return die("rt_write_pfm", rc);
+  if (!spp_map.empty()) {
+    std::vector<float> cnt(size_t(W) * H * 3);
+    for (size_t p = 0; p < counts.size(); ++p) cnt[3 * p] = cnt[3 * p + 1] = cnt[3 * p + 2] = float(counts[p]);
+    if ((rc = rt_write_pfm(spp_map.c_str(), cnt.data(), W, H, 1))) return die("rt_write_pfm", rc);
+  }
   return 0;
 }

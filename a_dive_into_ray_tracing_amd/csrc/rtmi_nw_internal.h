@@ -100,6 +100,13 @@ int ckpt_write(const char *path, const CkptHeader &h, const int64_t *raw);
 // another magic.  With raw: also the body, the header's W * nrows * 3 sums — RT_EIO when W < 1 or nrows <
 // 0, or when the file holds fewer or more bytes than that.
 int ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *raw);
+// Checkpoint file of the adaptive accumulator (rt_nw_adapt_save / _load / _info): the same header under the magic
+// "RTMINWD1" (spp_done: the largest count a pixel holds), then the int64 sums [nrows][W][3], the uint64 second
+// moments [nrows][W] and the int32 counts [nrows][W].  Written and read as the progressive file is: atomically;
+// RT_EIO for a file of another magic (a progressive checkpoint among them), a short one or a longer one.  The three
+// vectors are filled together or not at all (all null: the header alone).
+int adapt_ckpt_write(const char *path, const CkptHeader &h, const int64_t *sum, const uint64_t *m2, const int32_t *n);
+int adapt_ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *sum, std::vector<uint64_t> *m2, std::vector<int32_t> *n);
 // FNV-1a 64 of the camera's bytes (the shutter included)
 uint64_t camera_hash(const rt_nw_camera *cam);
 

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -2154,8 +2155,134 @@ int ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *raw) {
   return RT_OK;
 }
 
+namespace {
+constexpr char kAdaptMagic[8] = {'R', 'T', 'M', 'I', 'N', 'W', 'D', '1'};
+}
+
+int adapt_ckpt_write(const char *path, const CkptHeader &h_in, const int64_t *sum, const uint64_t *m2, const int32_t *n) {
+  if (!path || !sum || !m2 || !n || h_in.W < 1 || h_in.nrows < 1) return set_error(RT_EINVAL, "rt_nw_adapt_save: bad argument");
+  CkptHeader h = h_in;
+  std::memcpy(h.magic, kAdaptMagic, 8);
+  h.zero = 0;
+  const size_t npix = size_t(h.W) * size_t(h.nrows);
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE *fp = std::fopen(tmp.c_str(), "wb");
+  if (!fp) return set_error(RT_EIO, "rt_nw_adapt_save: cannot open %s", tmp.c_str());
+  bool ok = std::fwrite(&h, sizeof h, 1, fp) == 1 && std::fwrite(sum, sizeof(int64_t), npix * 3, fp) == npix * 3 &&
+            std::fwrite(m2, sizeof(uint64_t), npix, fp) == npix && std::fwrite(n, sizeof(int32_t), npix, fp) == npix;
+  if (std::fclose(fp) != 0) ok = false;
+  if (!ok || std::rename(tmp.c_str(), path) != 0) {
+    std::remove(tmp.c_str());
+    return set_error(RT_EIO, "rt_nw_adapt_save: write to %s failed", path);
+  }
+  return RT_OK;
+}
+
+int adapt_ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *sum, std::vector<uint64_t> *m2, std::vector<int32_t> *n) {
+  if (!path) return set_error(RT_EINVAL, "null path");
+  FILE *fp = std::fopen(path, "rb");
+  if (!fp) return set_error(RT_EIO, "cannot open %s", path);
+  CkptHeader r{};
+  if (std::fread(&r, sizeof r, 1, fp) != 1 || std::memcmp(r.magic, kAdaptMagic, 8) != 0) {
+    std::fclose(fp);
+    return set_error(RT_EIO, "%s is not a Next-Week adaptive checkpoint", path);
+  }
+  h = r;
+  if (!sum || !m2 || !n) {
+    std::fclose(fp);
+    return RT_OK;
+  }
+  // the body's size comes from the header: bounded before anything is allocated
+  const bool sane = r.W >= 1 && r.nrows >= 1 && int64_t(r.W) * r.nrows < (int64_t(1) << 40);
+  bool ok = sane && std::fseek(fp, 0, SEEK_END) == 0;
+  const long end = ok ? std::ftell(fp) : -1;
+  const uint64_t npix = sane ? uint64_t(r.W) * uint64_t(r.nrows) : 0;
+  ok = ok && end >= 0 && uint64_t(end) == sizeof r + npix * (3 * sizeof(int64_t) + sizeof(uint64_t) + sizeof(int32_t)) &&
+       std::fseek(fp, long(sizeof r), SEEK_SET) == 0;
+  if (ok) {
+    sum->resize(size_t(npix) * 3);
+    m2->resize(size_t(npix));
+    n->resize(size_t(npix));
+    ok = std::fread(sum->data(), sizeof(int64_t), size_t(npix) * 3, fp) == size_t(npix) * 3 &&
+         std::fread(m2->data(), sizeof(uint64_t), size_t(npix), fp) == size_t(npix) &&
+         std::fread(n->data(), sizeof(int32_t), size_t(npix), fp) == size_t(npix);
+  }
+  std::fclose(fp);
+  if (!ok) return set_error(RT_EIO, "%s is truncated, or holds more than its header states", path);
+  return RT_OK;
+}
+
 }  // namespace nw
 }  // namespace rtmi
+
+RTMI_EXPORT int rt_nw_adapt_info(const char *path, int32_t out8[8], uint64_t out3[3]) {
+  if (!path || !out8 || !out3) return set_error(RT_EINVAL, "rt_nw_adapt_info: null argument");
+  CkptHeader h{};
+  std::vector<int64_t> sum;
+  std::vector<uint64_t> m2;
+  std::vector<int32_t> n;
+  if (int rc = adapt_ckpt_read(path, h, &sum, &m2, &n)) return rc;  // (the body too: a truncated file is refused)
+  const int32_t v[8] = {h.W, h.H, h.row0, h.row_step, h.nrows, h.spp_done, h.max_depth, h.zero};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  out3[0] = h.seed;
+  out3[1] = h.scene_hash;
+  out3[2] = h.camera_hash;
+  return RT_OK;
+}
+
+// The stopping rule of adaptive sampling, per pixel in float64 (this file is compiled without contraction), in the
+// order the header states.  A pixel with fewer than two samples has no variance estimate: its err is +inf.  A
+// threshold of exactly 0 keeps every pixel below max_spp active.
+RTMI_EXPORT int rt_nw_adapt_criterion(const int64_t *sum, const uint64_t *m2, const int32_t *n, int32_t W, int32_t nrows,
+                                      int32_t min_spp, int32_t max_spp, double threshold, double floor, int32_t dilate,
+                                      uint8_t *active, double *err, int64_t *n_active) {
+  if (!sum || !m2 || !n || !active) return set_error(RT_EINVAL, "rt_nw_adapt_criterion: null argument");
+  if (W < 1 || nrows < 1 || int64_t(W) * nrows >= (int64_t(1) << 40)) return set_error(RT_EINVAL, "rt_nw_adapt_criterion: bad size");
+  if (min_spp < 0 || max_spp < 2 || min_spp > max_spp || max_spp > RT_NW_ADAPT_MAX_SPP)
+    return set_error(RT_EINVAL, "rt_nw_adapt_criterion: need 0 <= min_spp <= max_spp, 2 <= max_spp <= 2^20");
+  if (!(threshold >= 0.0) || !(floor > 0.0) || !std::isfinite(floor) || dilate < 0)
+    return set_error(RT_EINVAL, "rt_nw_adapt_criterion: need threshold >= 0, floor > 0 and dilate >= 0");
+  const size_t npix = size_t(W) * size_t(nrows);
+  const int32_t least = std::max(min_spp, 2);
+  dilate = std::min(dilate, std::max(W, nrows));  // (a wider window covers the strip already)
+  std::vector<uint8_t> raw(npix);
+  for (size_t p = 0; p < npix; ++p) {
+    const int32_t k = n[p];
+    if (k < 0) return set_error(RT_EINVAL, "rt_nw_adapt_criterion: negative sample count");
+    double e = std::numeric_limits<double>::infinity();
+    if (k >= 2) {
+      const double nn = double(k);
+      const double mean = double(sum[3 * p] + sum[3 * p + 1] + sum[3 * p + 2]) * 0x1p-32 / nn;
+      const double ex2 = double(m2[p]) * 0x1p-28 / nn;
+      const double var = std::max(0.0, ex2 - mean * mean) * nn / (nn - 1.0);
+      e = std::sqrt(var / nn) / std::max(mean, floor);
+    }
+    if (err) err[p] = e;
+    // (a threshold of 0 cannot be met, not even by equal samples, whose err is 0)
+    raw[p] = k < max_spp && (k < least || e > threshold || threshold == 0.0) ? 1 : 0;
+  }
+  // dilation by `dilate` pixels (a square window), never onto a pixel at max_spp: along rows, then along columns
+  std::vector<uint8_t> rows(raw);
+  if (dilate > 0) {
+    for (int32_t y = 0; y < nrows; ++y)
+      for (int32_t x = 0; x < W; ++x) {
+        uint8_t v = 0;
+        for (int32_t i = std::max(0, x - dilate); i <= std::min(W - 1, x + dilate) && !v; ++i) v = raw[size_t(y) * W + i];
+        rows[size_t(y) * W + x] = v;
+      }
+  }
+  int64_t count = 0;
+  for (int32_t y = 0; y < nrows; ++y)
+    for (int32_t x = 0; x < W; ++x) {
+      uint8_t v = 0;
+      for (int32_t j = std::max(0, y - dilate); j <= std::min(nrows - 1, y + dilate) && !v; ++j) v = rows[size_t(j) * W + x];
+      v = v && n[size_t(y) * W + x] < max_spp ? 1 : 0;
+      active[size_t(y) * W + x] = v;
+      count += v;
+    }
+  if (n_active) *n_active = count;
+  return RT_OK;
+}
 
 RTMI_EXPORT int rt_nw_accum_info(const char *path, int32_t out8[8], uint64_t out3[3]) {
   if (!path || !out8 || !out3) return set_error(RT_EINVAL, "rt_nw_accum_info: null argument");

@@ -18,9 +18,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import RtNwCamera, RtNwFlat, check, load
+from ._abi import NW_ADAPT_ON_PASS, RtNwAdaptStats, RtNwCamera, RtNwFlat, check, load
 
-__all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "accum_info", "SCENES"]
+__all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "accum_info", "SCENES",
+           "adapt_criterion", "adapt_info", "ADAPT_FLOOR"]
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -405,6 +406,39 @@ def accum_info(path):
     return d
 
 
+def adapt_info(path):
+    """The header of a Next-Week adaptive checkpoint file (host only, rt_nw_adapt_info);
+    spp_done is the largest count a pixel holds."""
+    v, u = (C.c_int32 * 8)(), (C.c_uint64 * 3)()
+    check(load().rt_nw_adapt_info(str(path).encode(), v, u), "rt_nw_adapt_info")
+    d = dict(zip(("W", "H", "row0", "row_step", "nrows", "spp_done", "max_depth", "zero"), list(v)))
+    d.update(zip(("seed", "scene_hash", "camera_hash"), list(u)))
+    return d
+
+
+# The channel-sum level below which adapt_criterion judges the error absolutely: a mean of 0.01 per channel,
+# level 25 of 255 after the square-root transfer (rtmi_nw.h).
+ADAPT_FLOOR = 0.03
+
+
+def adapt_criterion(s, m2, n, min_spp, max_spp, threshold, floor=ADAPT_FLOOR, dilate=1):
+    """Which pixels need more samples (host only, rt_nw_adapt_criterion): from
+    sum [nrows, W, 3], m2 and n [nrows, W] to (active uint8 [nrows, W], err
+    float64 [nrows, W], active count)."""
+    n = np.ascontiguousarray(n, np.int32)
+    if n.ndim != 2:
+        raise ValueError("adapt_criterion: n must be [nrows, W]")
+    s, m2 = np.ascontiguousarray(s, np.int64), np.ascontiguousarray(m2, np.uint64)
+    if s.shape != n.shape + (3,) or m2.shape != n.shape:
+        raise ValueError("adapt_criterion: sum [nrows, W, 3], m2 and n [nrows, W]")
+    active, err, count = np.zeros(n.shape, np.uint8), np.zeros(n.shape, np.float64), C.c_int64()
+    check(load().rt_nw_adapt_criterion(s.ctypes.data_as(C.POINTER(C.c_int64)), m2.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       n.ctypes.data_as(_ip), n.shape[1], n.shape[0], min_spp, max_spp, float(threshold),
+                                       float(floor), dilate, active.ctypes.data_as(_u8), err.ctypes.data_as(_dp),
+                                       C.byref(count)), "rt_nw_adapt_criterion")
+    return active, err, count.value
+
+
 def load_image(path):
     """Decode an image file (the earth texture) to h x w x 3 uint8, row 0 at the top (PIL)."""
     from PIL import Image
@@ -521,6 +555,102 @@ class NwRenderer:
             if on_pass is not None:
                 on_pass(done)
         return self.resolve()
+
+    # ---- adaptive sampling (rt_nw_adapt_*) --------------------------------
+    def adapt_reset(self, W, nrows):
+        """A zeroed adaptive accumulator (colour sums, second moments, counts) for a W x nrows strip."""
+        check(load().rt_nw_adapt_reset(self._h, W, nrows), "rt_nw_adapt_reset")
+        self._adapt_shape = (nrows, W)
+
+    def adapt_pass(self, cam, W, H, s_count, max_depth=50, seed=1984, row0=0, row_step=1, nrows=None, active=None, stream=0):
+        """Give every active pixel p the samples [n[p], n[p] + s_count) (async).
+        active: [nrows, W], nonzero = sample this pixel; None = all."""
+        nrows = H if nrows is None else nrows
+        ptr = None
+        if active is not None:
+            m = np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+            if m.shape != (nrows, W):
+                raise ValueError("adapt_pass: active must be [nrows, W]")
+            ptr = m.ctypes.data_as(_u8)
+        check(load().rt_nw_adapt_pass(self._h, C.byref(cam), W, H, s_count, max_depth, seed, row0, row_step, nrows, ptr,
+                                      C.c_void_p(stream)), "rt_nw_adapt_pass")
+
+    def adapt_export(self):
+        """(sum int64 [nrows, W, 3], m2 uint64 [nrows, W], n int32 [nrows, W])."""
+        sh = getattr(self, "_adapt_shape", (0, 0))
+        s, m2, n = np.zeros(sh + (3,), np.int64), np.zeros(sh, np.uint64), np.zeros(sh, np.int32)
+        check(load().rt_nw_adapt_export(self._h, s.ctypes.data_as(C.POINTER(C.c_int64)), m2.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        n.ctypes.data_as(_ip), n.size), "rt_nw_adapt_export")
+        return s, m2, n
+
+    def adapt_import(self, s, m2, n):
+        s, m2, n = np.ascontiguousarray(s, np.int64), np.ascontiguousarray(m2, np.uint64), np.ascontiguousarray(n, np.int32)
+        if s.size != 3 * n.size or m2.size != n.size:
+            raise ValueError("adapt_import: sum [nrows, W, 3], m2 and n [nrows, W]")
+        check(load().rt_nw_adapt_import(self._h, s.ctypes.data_as(C.POINTER(C.c_int64)), m2.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        n.ctypes.data_as(_ip), n.size), "rt_nw_adapt_import")
+
+    def adapt_resolve(self, dev_ptr=None, stream=0):
+        """The per-pixel means float(double(sum) * 2^-32 / n), 0 where n = 0: into
+        the device strip dev_ptr (asynchronous), else a host array [nrows, W, 3]."""
+        if dev_ptr is not None:
+            check(load().rt_nw_adapt_resolve(self._h, C.c_void_p(dev_ptr), None, C.c_void_p(stream)), "rt_nw_adapt_resolve")
+            return None
+        out = np.zeros(getattr(self, "_adapt_shape", (0, 0)) + (3,), np.float32)
+        check(load().rt_nw_adapt_resolve(self._h, None, out.ctypes.data_as(_fp), C.c_void_p(stream)), "rt_nw_adapt_resolve")
+        return out
+
+    def adapt_save(self, path, cam, H, max_depth=50, seed=1984, row0=0, row_step=1):
+        check(load().rt_nw_adapt_save(self._h, str(path).encode(), self._scene._h, C.byref(cam), H, row0, row_step, max_depth,
+                                      seed), "rt_nw_adapt_save")
+
+    def adapt_load(self, path, cam, W, H, max_depth=50, seed=1984, row0=0, row_step=1, nrows=None):
+        nrows = H if nrows is None else nrows
+        check(load().rt_nw_adapt_load(self._h, str(path).encode(), self._scene._h, C.byref(cam), W, H, row0, row_step, nrows,
+                                      max_depth, seed), "rt_nw_adapt_load")
+        self._adapt_shape = (nrows, W)
+
+    def adaptive(self, cam, W, H, min_spp, max_spp, pass_spp, threshold, floor=ADAPT_FLOOR, dilate=1, max_depth=50, seed=1984,
+                 checkpoint=None, time_limit=None, on_pass=None, stats=None):
+        """Sample until no pixel's relative error (adapt_criterion) exceeds
+        `threshold`, no pixel above max_spp samples, in passes of pass_spp over
+        the active pixels (rt_nw_render_adaptive); resumes from `checkpoint` when
+        that file exists and saves to it after every pass; on_pass(pass number,
+        pixels it sampled) is called after each, and an exception it raises ends
+        the run and is raised again here; time_limit (seconds): no new pass after
+        that long (one always runs).  Returns (mean [H, W, 3] float32, n [H, W]
+        int32, err [H, W] float64); stats (a dict, when given) receives passes,
+        stopped, total_samples, pixels_at_max, samples and segments (this call's)
+        and active (pixels per pass)."""
+        mean, n, err = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.int32), np.zeros((H, W), np.float64)
+        # (pixels join at different passes, so there can be more than max_spp / pass_spp of them; the log keeps
+        # the first 4 max_spp / pass_spp + 64)
+        log = np.zeros(4 * -(-max(max_spp, 1) // max(pass_spp, 1)) + 64, np.int64)
+        st = RtNwAdaptStats(active=log.ctypes.data_as(C.POINTER(C.c_int64)), cap=log.size)
+        raised = []
+
+        def step(_user, k, count):
+            try:
+                on_pass(k, count)
+            except BaseException as e:  # (must not cross the C frames)
+                raised.append(e)
+                return 1
+            return 0
+
+        cb = NW_ADAPT_ON_PASS(step) if on_pass is not None else NW_ADAPT_ON_PASS()
+        check(load().rt_nw_render_adaptive(self._h, self._scene._h, C.byref(cam), W, H, min_spp, max_spp, pass_spp,
+                                           float(threshold), float(floor), dilate, max_depth, seed,
+                                           None if checkpoint is None else str(checkpoint).encode(),
+                                           -1.0 if time_limit is None else float(time_limit), mean.ctypes.data_as(_fp),
+                                           n.ctypes.data_as(_ip), err.ctypes.data_as(_dp), C.byref(st), cb, None),
+              "rt_nw_render_adaptive")
+        self._adapt_shape = (H, W)
+        if stats is not None:
+            stats.update(passes=st.passes, stopped=st.stopped, total_samples=st.total_samples, pixels_at_max=st.pixels_at_max,
+                         samples=st.samples, segments=st.segments, active=[int(v) for v in log[:min(st.passes, log.size)]])
+        if raised:
+            raise raised[0]
+        return mean, n, err
 
     def debug_trace(self, cam, W, H, i, j, s, max_depth=50, seed=1984, cap=64, with_time=False):
         """The segments of one camera sample: rows (o.xyz, d.xyz, t, n.xyz) and (winner index, box face);

@@ -404,6 +404,115 @@ int rt_nw_accum_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const
 int rt_nw_accum_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
                      int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed, int32_t *spp_done);
 int rt_nw_accum_info(const char *path, int32_t out8[8], uint64_t out3[3]);
+/* Adaptive sampling (DESIGN.md §9 "Adaptive sampling").  A third accumulator of
+ * the context, allocations of its own that plain renders and progressive
+ * passes in between do not touch.  For a W x nrows strip it holds
+ *   sum  int64  [nrows][W][3]  the colour sums, as the pass accumulator's;
+ *   m2   uint64 [nrows][W]     the sum over the pixel's samples of l^2, where
+ *                              l = (fx + fy + fz) >> 18 and fx, fy, fz are the
+ *                              sample's three 2^-32 fixed-point values: the
+ *                              channel sum in units of 2^-14, below 2^22;
+ *   n    int32  [nrows][W]     the samples the pixel holds.
+ * A pixel holds at most RT_NW_ADAPT_MAX_SPP = 2^20 samples: a sample's l is at
+ * most 192 * 2^14, and 192^2 * 2^28 * 2^20 < 2^64, so m2 cannot overflow.
+ * rt_nw_adapt_reset allocates and zeroes the accumulator.
+ * rt_nw_adapt_pass gives every active pixel p the samples [n[p], n[p] +
+ * s_count).  `active` is a HOST array of W * nrows bytes, nonzero = sample this
+ * pixel; NULL = every pixel (pixels of rows past H are never sampled).  It
+ * validates as rt_nw_render_pass does and also refuses (RT_EINVAL) s_count < 0,
+ * an accumulator of another W x nrows and a pass that would take an active
+ * pixel past 2^20 samples (nothing is then changed).  An all-zero mask or
+ * s_count == 0 succeeds, launches nothing, and rt_nw_ctx_last_segments is 0.
+ * The pass is asynchronous on `stream`: its tile list is uploaded in stream
+ * order into one of two device lists, so the host waits only for the pass
+ * before the last one, which used that list.
+ * Contract: after any sequence of passes with any masks, pixel p's sum equals
+ * the pass accumulator's raw int64 sums at p after rt_nw_render_pass(s_begin =
+ * 0, s_count = n[p]), bit for bit, under any kernel shape, accelerator, staging
+ * path or RTMI_NW_CHUNK; m2[p] is the sum over s < n[p] of l_s^2.  An
+ * all-active pass counts the segments of that rt_nw_render_pass.
+ * rt_nw_adapt_export / _import copy (sum, m2, n) out / in (npix = W * nrows;
+ * import refuses a count outside [0, 2^20]).  rt_nw_adapt_resolve writes the
+ * per-pixel MEANS float(double(sum) * 2^-32 / n), 0 where n = 0 (sums mean
+ * nothing with unequal counts), into a DEVICE strip and/or a HOST buffer
+ * (W*nrows*3), as rt_nw_accum_resolve does. */
+#define RT_NW_ADAPT_MAX_SPP (1 << 20)
+int rt_nw_adapt_reset(rt_nw_ctx *ctx, int32_t W, int32_t nrows);
+int rt_nw_adapt_pass(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t s_count, int32_t max_depth,
+                     uint64_t seed, int32_t row0, int32_t row_step, int32_t nrows, const uint8_t *active, void *stream);
+int rt_nw_adapt_export(rt_nw_ctx *ctx, int64_t *sum, uint64_t *m2, int32_t *n, size_t npix);
+int rt_nw_adapt_import(rt_nw_ctx *ctx, const int64_t *sum, const uint64_t *m2, const int32_t *n, size_t npix);
+int rt_nw_adapt_resolve(rt_nw_ctx *ctx, float *dev_mean, float *host_mean, void *stream);
+/* Host only, pure (no device): which pixels need more samples.  Per pixel, in
+ * float64, in this order, without contraction:
+ *   mean = (Sx + Sy + Sz) * 2^-32 / n        (the integer channel sum, exact)
+ *   ex2  = m2 * 2^-28 / n
+ *   var  = max(0, ex2 - mean * mean) * n / (n - 1)
+ *   err  = sqrt(var / n) / max(mean, floor)
+ * and err = +inf where n < 2.  A pixel is active when n < max(min_spp, 2), or
+ * when err > threshold and n < max_spp.  A threshold of exactly 0 cannot be
+ * met, not even by a pixel whose samples are all equal (err = 0, as of a pixel
+ * that sees the background alone): every pixel below max_spp is then active,
+ * and the driver's result is the plain render of max_spp samples.  For any
+ * threshold above 0 such a pixel stops at min_spp; so does a pixel whose first
+ * min_spp samples all missed a small light, which is why min_spp must not be
+ * too small for the scene.  The mask is then dilated by `dilate`
+ * pixels (a square window; 1 is the drivers' default), never onto a pixel at
+ * max_spp.  err is the relative standard error of the pixel's mean channel sum;
+ * below `floor` (a channel-sum level; the drivers' default 0.03: a mean of
+ * 0.01 per channel, level 25 of 255 after the square-root transfer) the error
+ * is judged absolutely, in units of floor, so that near-black pixels do not ask
+ * for samples for ever.  m2 is quantised (l drops 18 bits) while the mean is
+ * exact: l^2 is low by less than 2 l units of 2^-28 per sample, so ex2 is low
+ * by less than 2^-13 * mean and err^2 by less than 2^-13 / ((n - 1) *
+ * max(mean, floor)), under 0.0041 / (n - 1) at the default floor (DESIGN.md
+ * §9).  active (W * nrows bytes) is required, err (W *
+ * nrows doubles) and n_active may be null.  RT_EINVAL unless 0 <= min_spp <=
+ * max_spp, 2 <= max_spp <= 2^20, threshold >= 0, floor > 0, dilate >= 0. */
+int rt_nw_adapt_criterion(const int64_t *sum, const uint64_t *m2, const int32_t *n, int32_t W, int32_t nrows, int32_t min_spp,
+                          int32_t max_spp, double threshold, double floor, int32_t dilate, uint8_t *active, double *err,
+                          int64_t *n_active);
+/* The driver: a whole W x H image sampled until no pixel is active.  Loop:
+ * export, criterion, and a pass of min(pass_spp, max_spp - the largest active
+ * count) samples over the active pixels, so no pixel passes max_spp; it ends
+ * when nothing is active or, with time_limit >= 0 (seconds; < 0: none), once
+ * that much time has passed since the first pass began (one pass always runs).
+ * checkpoint (may be null; needs `scene`): resumed from when the file exists,
+ * saved after every pass.  Outputs, each may be null: mean_out W*H*3 floats
+ * (rt_nw_adapt_resolve), n_out W*H counts, err_out W*H doubles (the final
+ * criterion's), stats.  on_pass (may be null) is called after every pass, and
+ * after its checkpoint is saved, with `user`, the pass number from 1 and the
+ * pixels that pass sampled; a nonzero return ends the run there (stopped = 2)
+ * with the outputs of the samples so far.  The result depends on the arguments alone: an
+ * interrupted and resumed run equals the uninterrupted one. */
+typedef struct rt_nw_adapt_stats {
+  int32_t passes;         /* passes this call ran */
+  int32_t stopped;        /* 0: nothing was active any more; 1: the time limit; 2: on_pass returned nonzero */
+  int64_t total_samples;  /* sum of n over the image */
+  int64_t pixels_at_max;  /* pixels with n >= max_spp */
+  int64_t samples;        /* samples this call rendered (less than total_samples after a resume) */
+  int64_t segments;       /* world.hit calls of this call's passes */
+  int64_t *active;        /* in: caller's array or null; out: active pixels of pass k, k < cap */
+  int32_t cap, pad;
+} rt_nw_adapt_stats;
+typedef int (*rt_nw_adapt_on_pass)(void *user, int32_t pass, int64_t active);
+int rt_nw_render_adaptive(rt_nw_ctx *ctx, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t min_spp,
+                          int32_t max_spp, int32_t pass_spp, double threshold, double floor, int32_t dilate, int32_t max_depth,
+                          uint64_t seed, const char *checkpoint, double time_limit, float *mean_out, int32_t *n_out,
+                          double *err_out, rt_nw_adapt_stats *stats, rt_nw_adapt_on_pass on_pass, void *user);
+/* Checkpoints of the adaptive accumulator: the progressive file's 64-byte
+ * header under the magic "RTMINWD1" (its spp_done field: the largest count a
+ * pixel holds), then sum, m2 and n as laid out above.  Refusals and the atomic
+ * write as rt_nw_accum_save / _load: RT_EINVAL ("made for another render"),
+ * RT_EIO for a missing, truncated or overlong file or another magic — a
+ * progressive checkpoint is refused here and an adaptive one by
+ * rt_nw_accum_load.  rt_nw_adapt_info (host only): the header as
+ * rt_nw_accum_info gives it, after checking the file's length. */
+int rt_nw_adapt_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t H, int32_t row0,
+                     int32_t row_step, int32_t max_depth, uint64_t seed);
+int rt_nw_adapt_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
+                     int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed);
+int rt_nw_adapt_info(const char *path, int32_t out8[8], uint64_t out3[3]);
 /* Host only (no device needed): FNV-1a 64 over everything of the scene that
  * can change a pixel, and nothing else — no address, not the accelerator
  * setting, no BVH or grid.  The same value in any process that builds the
