@@ -448,7 +448,7 @@ __device__ __forceinline__ void add_segments(unsigned nseg, int lane, unsigned l
   if (lane == 0) atomicAdd(segments, (unsigned long long)nseg);  // the wave's world.hit calls (wave-uniform)
 }
 
-// TRI (last parameter of both kernels): the scene holds no triangle (0), triangles (1), triangles with
+// TRI: the scene holds no triangle (0), triangles (1), triangles with
 // attribute records (2; hit_object, make_rec), placements of shared meshes (3; hit_world_nw_inst: BVH
 // shapes only, such a scene has no uniform grid), placements of which some move (4; the same walk with
 // the moving placements' offsets formed at the ray's time), placements of which some are affine (5; the
@@ -474,8 +474,12 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel(View sc, Args a, un
 #ifndef RTMI_NW_PERSIST_GRID_PER_EU
 #define RTMI_NW_PERSIST_GRID_PER_EU 1
 #endif
+// minimum waves per SIMD a persistent kernel (and its adaptive twin) is compiled for
+constexpr int persist_per_eu(bool s, bool grid, int tri) {
+  return s ? RTMI_NW_SIMPLE_PER_EU : grid ? RTMI_NW_PERSIST_GRID_PER_EU : tri >= 4 ? affine_per_eu(tri) : tri == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU;
+}
 template <bool CHUNKED, bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
-__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI >= 4 ? affine_per_eu(TRI) : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent(View sc, Args a,
+__global__ __launch_bounds__(64 * persist_waves<S>(), persist_per_eu(S, GRID, TRI)) void render_persistent(View sc, Args a,
                                                                   unsigned long long *__restrict__ accum,
                                                                   float *__restrict__ out,
                                                                   unsigned long long *__restrict__ segments,
@@ -519,7 +523,7 @@ __global__ __launch_bounds__(64 * kWaves) void render_kernel_adapt(View sc, Args
 }
 
 template <bool LDS_OBJS, bool GRID, bool S = false, int TRI = 0>
-__global__ __launch_bounds__(64 * persist_waves<S>(), S ? RTMI_NW_SIMPLE_PER_EU : (GRID ? RTMI_NW_PERSIST_GRID_PER_EU : (TRI >= 4 ? affine_per_eu(TRI) : TRI == 3 ? RTMI_NW_INST_PER_EU : RTMI_NW_PERSIST_PER_EU))) void render_persistent_adapt(View sc, Args a, AdaptArgs ad,
+__global__ __launch_bounds__(64 * persist_waves<S>(), persist_per_eu(S, GRID, TRI)) void render_persistent_adapt(View sc, Args a, AdaptArgs ad,
                                                                   unsigned long long *__restrict__ accum,
                                                                   unsigned long long *__restrict__ segments,
                                                                   unsigned *__restrict__ counter) {
@@ -563,16 +567,41 @@ __global__ void adapt_resolve_kernel(const unsigned long long *__restrict__ sum,
     out[3 * i + c] = k > 0 ? float(double((long long)sum[3 * i + c]) * 0x1p-32 / double(k)) : 0.0f;
 }
 
+// The walks of the validation kernels below, one instantiation each: the BVH from global memory; the uniform grid
+// staged in LDS as the grid kernels stage it; the two-level walk of a scene with placements of shared meshes
+// (hit_world_nw_inst's modes: static, some move, some are affine), nodes and records in global memory.
+enum Walk { kWalkBvh, kWalkGrid, kWalkInst, kWalkMove, kWalkAffine, kWalks };
+
+// closest hit of one ray through WALK (TRI: the triangle code of the one-level walks; sub: the winner's pool slot
+// when it is a placement's triangle), the winner's insertion index and its hit record
+template <int WALK, int TRI>
+__device__ __forceinline__ int32_t walk_closest(const View &sc, const V &o, const V &d, float time, uint64_t key, float &t,
+                                                int &face, int32_t &sub, NwCount *cnt) {
+  if constexpr (WALK >= kWalkInst) return hit_world_nw_inst<false, false, WALK - kWalkInst>(sc, o, d, time, key, t, face, sub, cnt);
+  else if constexpr (WALK == kWalkGrid) return hit_world_nw_grid<false, TRI>(sc, o, d, time, key, t, face, cnt);
+  else return hit_world_nw<false, false, TRI>(sc, o, d, time, key, t, face, cnt);
+}
+template <int WALK> __device__ __forceinline__ int32_t walk_winner_id(const View &sc, int32_t k, int32_t sub) {
+  if (k < 0) return -1;
+  if (k >= sc.nobj) return sc.med_id[k - sc.nobj];
+  if constexpr (WALK >= kWalkInst) return inst_winner_id(sc, k, sub);
+  else return sc.obj_id[k];
+}
+template <int WALK>
+__device__ __forceinline__ Rec walk_rec(const View &sc, int32_t k, int32_t sub, const V &o, const V &d, float time, float t,
+                                        int face, int has_attr) {
+  if (k >= sc.nobj) return make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time);
+  if constexpr (WALK >= kWalkInst) return make_rec_inst<WALK - kWalkInst>(sc, k, sub, o, d, time, t, face);
+  else return make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr}, k);
+}
+
 // Debug (parity investigations): the segments of ONE camera sample (pixel
 // i, j, sample s): per segment o.xyz, d.xyz, t, winner insertion index (as
 // float bits) — the oracle's or_nw_trace records the same.
-// has_attr: the scene has triangle attribute records (attr_view_of).
-// INST: a scene with placements of shared meshes (the two-level walk); 2: some of them move; 3: some are affine.
-template <int INST>
-__device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i, int j, int s, float *rec, int cap, int *n_out,
-                                           int has_attr) {
+// has_attr: the scene has triangle attribute records (attr_view_of; the two-level walks do not read it).
+template <int WALK>
+__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const AttrView av = has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr};
   Xoro rng;
   rng.init(a.seed, uint64_t(j) * uint64_t(a.W) + uint64_t(i), uint32_t(s));
   float ju, jv;
@@ -589,17 +618,14 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
     float t;
     int face;
     int32_t sub = -1;
-    const int32_t k = INST ? hit_world_nw_inst<false, false, INST - 1>(sc, o, d, time, seg_key, t, face, sub, &tcnt)
-                           : hit_world_nw<false, false, 2>(sc, o, d, time, seg_key, t, face, &tcnt);
+    const int32_t k = walk_closest<WALK, 2>(sc, o, d, time, seg_key, t, face, sub, &tcnt);
     float *r = rec + 12 * n++;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z; r[6] = t;
-    r[7] = __int_as_float(k < 0 ? -1 : k < sc.nobj ? (INST ? inst_winner_id(sc, k, sub) : sc.obj_id[k]) : sc.med_id[k - sc.nobj]);
+    r[7] = __int_as_float(walk_winner_id<WALK>(sc, k, sub));
     r[8] = r[9] = r[10] = 0.f;
     r[11] = __int_as_float(face);
     if (k < 0) break;
-    const Rec rc = k >= sc.nobj ? make_rec_medium(sc, sc.med[k - sc.nobj], o, d, time)
-                   : INST       ? make_rec_inst<INST - 1>(sc, k, sub, o, d, time, t, face)
-                                : make_rec<false, 2>(sc, sc.obj[k], o, d, time, t, face, av, k);
+    const Rec rc = walk_rec<WALK>(sc, k, sub, o, d, time, t, face, has_attr);
     r[8] = rc.n.x; r[9] = rc.n.y; r[10] = rc.n.z;
     const Mat m = sc.mat[rc.mat];
     V at, nd;
@@ -609,19 +635,7 @@ __device__ __forceinline__ void trace_body(const View &sc, const Args &a, int i,
   }
   *n_out = n;
 }
-__global__ void trace_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out, int has_attr) {
-  trace_body<0>(sc, a, i, j, s, rec, cap, n_out, has_attr);
-}
-__global__ void trace_inst_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
-  trace_body<1>(sc, a, i, j, s, rec, cap, n_out, 0);
-}
-__global__ void trace_move_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
-  trace_body<2>(sc, a, i, j, s, rec, cap, n_out, 0);
-}
-__global__ void trace_affine_kernel(View sc, Args a, int i, int j, int s, float *rec, int cap, int *n_out) {
-  trace_body<3>(sc, a, i, j, s, rec, cap, n_out, 0);
-}
-// The ray time of that camera sample (rt_nw_debug_trace_t): trace_body's draws up to the time
+// The ray time of that camera sample (rt_nw_debug_trace_t): trace_kernel's draws up to the time
 __global__ void trace_time_kernel(Args a, int i, int j, int s, float *time_out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   Xoro rng;
@@ -638,159 +652,63 @@ __global__ void finalize_kernel(const unsigned long long *__restrict__ acc, floa
   if (i < n) out[i] = float((long long)acc[i]) * 0x1p-32f;
 }
 
-// Closest hit of n given rays through the walk the renders use (validation:
-// rt_nw_debug_hits): the uniform grid staged in LDS as the grid kernels stage
-// it (GRID), or the BVH from global memory.  rays: {o.xyz, d.xyz, time, -} per
-// ray; keys: the segments' medium keys (null: 0).
-template <bool GRID>
-__global__ __launch_bounds__(256) void debug_hits_kernel(View sc, const float *__restrict__ rays,
-                                                         const unsigned long long *__restrict__ keys, int32_t n,
-                                                         int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                         int32_t *__restrict__ out_face) {
-  stage_scene<false, false, GRID>(sc);  // (GRID: ends with the block barrier, before any thread leaves)
+// The rays and the outputs of rt_nw_debug_hits / rt_nw_debug_records, per ray
+struct DebugRays {
+  const float *rays;               // {o.xyz, d.xyz, time, -}
+  const unsigned long long *keys;  // the segments' medium keys (null: 0)
+  int32_t n, has_attr;             // has_attr: as trace_kernel's (records only)
+  int32_t *id;                     // out: the winner's insertion index (-1: miss)
+  float *t;
+  int32_t *aux;                    // out: the box face (hits), the material (records)
+  float *pnuv;                     // out, records only: {p.xyz, n.xyz, u, v}
+};
+
+// Closest hit of n given rays through the walk the renders use (validation: rt_nw_debug_hits).
+template <int WALK> __global__ __launch_bounds__(256) void debug_hits_kernel(View sc, DebugRays q) {
+  stage_scene<false, false, WALK == kWalkGrid>(sc);  // (grid: ends with the block barrier, before any thread leaves)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float *r = rays + 8 * size_t(i);
+  if (i >= q.n) return;
+  const float *r = q.rays + 8 * size_t(i);
   const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
   NwCount cnt{0, 0, 0, 0};
   float t;
   int face;
-  const int32_t k = GRID ? hit_world_nw_grid<false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
-                         : hit_world_nw<false, false, 1>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
-  out_id[i] = k < 0 ? -1 : k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
-  out_t[i] = t;
-  out_face[i] = face;
-}
-// ... of a scene with placements of shared meshes: the two-level walk, nodes
-// and records in global memory
-template <int MOVE>
-__device__ __forceinline__ void debug_hits_inst_body(const View &sc, const float *__restrict__ rays,
-                                                     const unsigned long long *__restrict__ keys, int32_t n,
-                                                     int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                     int32_t *__restrict__ out_face) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float *r = rays + 8 * size_t(i);
-  const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
-  NwCount cnt{0, 0, 0, 0};
-  float t;
-  int face;
-  int32_t sub;
-  const int32_t k = hit_world_nw_inst<false, false, MOVE>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
-  out_id[i] = k < 0 ? -1 : k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
-  out_t[i] = t;
-  out_face[i] = face;
-}
-__global__ __launch_bounds__(256) void debug_hits_inst_kernel(View sc, const float *__restrict__ rays,
-                                                              const unsigned long long *__restrict__ keys, int32_t n,
-                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                              int32_t *__restrict__ out_face) {
-  debug_hits_inst_body<0>(sc, rays, keys, n, out_id, out_t, out_face);
-}
-// ... some of whose placements move (TRI = 4)
-__global__ __launch_bounds__(256) void debug_hits_move_kernel(View sc, const float *__restrict__ rays,
-                                                              const unsigned long long *__restrict__ keys, int32_t n,
-                                                              int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                              int32_t *__restrict__ out_face) {
-  debug_hits_inst_body<1>(sc, rays, keys, n, out_id, out_t, out_face);
-}
-// ... some of whose placements are affine (TRI = 5)
-__global__ __launch_bounds__(256) void debug_hits_affine_kernel(View sc, const float *__restrict__ rays,
-                                                                const unsigned long long *__restrict__ keys, int32_t n,
-                                                                int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                                int32_t *__restrict__ out_face) {
-  debug_hits_inst_body<2>(sc, rays, keys, n, out_id, out_t, out_face);
+  int32_t sub = -1;
+  const int32_t k = walk_closest<WALK, 1>(sc, o, d, r[6], q.keys ? q.keys[i] : 0ull, t, face, sub, &cnt);
+  q.id[i] = walk_winner_id<WALK>(sc, k, sub);
+  q.t[i] = t;
+  q.aux[i] = face;
 }
 
 // The hit record of n given rays (validation: rt_nw_debug_records): the
 // closest hit as debug_hits_kernel resolves it, then the record a render makes
-// of it (make_rec with the attribute path, make_rec_medium).  Out per ray: the
-// winner's insertion index (-1: miss, everything else zero), t, {p.xyz, n.xyz,
-// u, v} and the material.
-template <bool GRID>
-__global__ __launch_bounds__(256) void debug_records_kernel(View sc, const float *__restrict__ rays,
-                                                            const unsigned long long *__restrict__ keys, int32_t n,
-                                                            int has_attr, int32_t *__restrict__ out_id,
-                                                            float *__restrict__ out_t, float *__restrict__ out_pnuv,
-                                                            int32_t *__restrict__ out_mat) {
-  stage_scene<false, false, GRID>(sc);  // (GRID: ends with the block barrier, before any thread leaves)
+// of it (make_rec with the attribute path, make_rec_inst, make_rec_medium).  A miss: index -1, everything else zero.
+template <int WALK> __global__ __launch_bounds__(256) void debug_records_kernel(View sc, DebugRays q) {
+  stage_scene<false, false, WALK == kWalkGrid>(sc);  // (grid: ends with the block barrier, before any thread leaves)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float *r = rays + 8 * size_t(i);
+  if (i >= q.n) return;
+  const float *r = q.rays + 8 * size_t(i);
   const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
   NwCount cnt{0, 0, 0, 0};
   float t;
   int face;
-  const int32_t k = GRID ? hit_world_nw_grid<false, 2>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt)
-                         : hit_world_nw<false, false, 2>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, &cnt);
-  float *q = out_pnuv + 8 * size_t(i);
+  int32_t sub = -1;
+  const int32_t k = walk_closest<WALK, 2>(sc, o, d, r[6], q.keys ? q.keys[i] : 0ull, t, face, sub, &cnt);
+  float *p = q.pnuv + 8 * size_t(i);
   if (k < 0) {
-    out_id[i] = -1;
-    out_t[i] = 0.0f;
-    out_mat[i] = 0;
-    for (int c = 0; c < 8; ++c) q[c] = 0.0f;
+    q.id[i] = -1;
+    q.t[i] = 0.0f;
+    q.aux[i] = 0;
+    for (int c = 0; c < 8; ++c) p[c] = 0.0f;
     return;
   }
-  const AttrView av = has_attr ? attr_view_of(sc) : AttrView{nullptr, nullptr};
-  const Rec rc = k < sc.nobj ? make_rec<false, 2>(sc, sc.obj[k], o, d, r[6], t, face, av, k)
-                             : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
-  out_id[i] = k < sc.nobj ? sc.obj_id[k] : sc.med_id[k - sc.nobj];
-  out_t[i] = t;
-  out_mat[i] = rc.mat;
-  q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
-  q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
-  q[6] = rc.u; q[7] = rc.v;
-}
-// ... of a scene with placements of shared meshes (as debug_hits_inst_kernel)
-template <int MOVE>
-__device__ __forceinline__ void debug_records_inst_body(const View &sc, const float *__restrict__ rays,
-                                                        const unsigned long long *__restrict__ keys, int32_t n,
-                                                        int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                        float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float *r = rays + 8 * size_t(i);
-  const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
-  NwCount cnt{0, 0, 0, 0};
-  float t;
-  int face;
-  int32_t sub;
-  const int32_t k = hit_world_nw_inst<false, false, MOVE>(sc, o, d, r[6], keys ? keys[i] : 0ull, t, face, sub, &cnt);
-  float *q = out_pnuv + 8 * size_t(i);
-  if (k < 0) {
-    out_id[i] = -1;
-    out_t[i] = 0.0f;
-    out_mat[i] = 0;
-    for (int c = 0; c < 8; ++c) q[c] = 0.0f;
-    return;
-  }
-  const Rec rc = k < sc.nobj ? make_rec_inst<MOVE>(sc, k, sub, o, d, r[6], t, face) : make_rec_medium(sc, sc.med[k - sc.nobj], o, d, r[6]);
-  out_id[i] = k < sc.nobj ? inst_winner_id(sc, k, sub) : sc.med_id[k - sc.nobj];
-  out_t[i] = t;
-  out_mat[i] = rc.mat;
-  q[0] = rc.p.x; q[1] = rc.p.y; q[2] = rc.p.z;
-  q[3] = rc.n.x; q[4] = rc.n.y; q[5] = rc.n.z;
-  q[6] = rc.u; q[7] = rc.v;
-}
-__global__ __launch_bounds__(256) void debug_records_inst_kernel(View sc, const float *__restrict__ rays,
-                                                                 const unsigned long long *__restrict__ keys, int32_t n,
-                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  debug_records_inst_body<0>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
-}
-// ... some of whose placements move (TRI = 4)
-__global__ __launch_bounds__(256) void debug_records_move_kernel(View sc, const float *__restrict__ rays,
-                                                                 const unsigned long long *__restrict__ keys, int32_t n,
-                                                                 int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                                 float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  debug_records_inst_body<1>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
-}
-// ... some of whose placements are affine (TRI = 5)
-__global__ __launch_bounds__(256) void debug_records_affine_kernel(View sc, const float *__restrict__ rays,
-                                                                   const unsigned long long *__restrict__ keys, int32_t n,
-                                                                   int32_t *__restrict__ out_id, float *__restrict__ out_t,
-                                                                   float *__restrict__ out_pnuv, int32_t *__restrict__ out_mat) {
-  debug_records_inst_body<2>(sc, rays, keys, n, out_id, out_t, out_pnuv, out_mat);
+  const Rec rc = walk_rec<WALK>(sc, k, sub, o, d, r[6], t, face, q.has_attr);
+  q.id[i] = walk_winner_id<WALK>(sc, k, sub);
+  q.t[i] = t;
+  q.aux[i] = rc.mat;
+  p[0] = rc.p.x; p[1] = rc.p.y; p[2] = rc.p.z;
+  p[3] = rc.n.x; p[4] = rc.n.y; p[5] = rc.n.z;
+  p[6] = rc.u; p[7] = rc.v;
 }
 
 }  // namespace nw
@@ -807,6 +725,38 @@ using namespace rtmi::nw;
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) return set_error(RT_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+namespace {
+
+struct Guard {
+  int prev = -1;
+  explicit Guard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(dev);
+  }
+  ~Guard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// A device allocation that is freed on every path out of its scope
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T)); }
+  hipError_t upload(const T *src, size_t count) {  // allocated here
+    const hipError_t e = alloc(count);
+    return e != hipSuccess ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  hipError_t download(T *dst, size_t count) const { return hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost); }
+};
+
+}  // namespace
 
 struct rt_nw_ctx {
   int device = 0;
@@ -897,20 +847,27 @@ struct rt_nw_ctx {
   // another stream first waits for the end of the last one (as rt_ctx)
   hipStream_t last_stream = nullptr;
   hipEvent_t last_done = nullptr;
+
+  rt_nw_ctx() = default;
+  rt_nw_ctx(const rt_nw_ctx &) = delete;
+  rt_nw_ctx &operator=(const rt_nw_ctx &) = delete;
+  ~rt_nw_ctx() {  // whatever has been made: rt_nw_ctx_destroy, and rt_nw_ctx_create's failure returns
+    Guard g(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (void *p : {(void *)obj, (void *)obj_id, (void *)med, (void *)med_id, (void *)inst, (void *)mat, (void *)tex, (void *)pvec,
+                    (void *)pperm, (void *)img, (void *)imgd, (void *)nodes, (void *)accum, (void *)scratch, (void *)segments,
+                    (void *)counter, (void *)grid_cells, (void *)grid_refs, (void *)grid_big, (void *)pass_accum, (void *)adapt_sum,
+                    (void *)adapt_m2, (void *)adapt_n, (void *)adapt_list[0].tiles, (void *)adapt_list[0].masks,
+                    (void *)adapt_list[1].tiles, (void *)adapt_list[1].masks})
+      if (p) (void)hipFree(p);
+    for (auto &l : adapt_list)
+      if (l.done) (void)hipEventDestroy(l.done);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (last_done) (void)hipEventDestroy(last_done);
+  }
 };
 
 namespace {
-
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(dev);
-  }
-  ~Guard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 template <class T> int alloc_copy(T **p, const T *src, size_t count) {
   if (*p) (void)hipFree(*p);
@@ -957,6 +914,83 @@ View view_of(const rt_nw_ctx *c) {
   return v;
 }
 
+// the camera's part of the kernels' arguments (everything else zero)
+Args camera_args(const rt_nw_camera *cam, int32_t W, int32_t H, int32_t max_depth, uint64_t seed) {
+  Args a{};
+  a.cam = camf(cam->cam);
+  a.time0 = float(cam->time0);
+  a.time1 = float(cam->time1);
+  a.W = W;
+  a.H = H;
+  a.max_depth = max_depth;
+  a.seed = seed;
+  return a;
+}
+
+// ---------------------------------------------------------------------------
+// The kernel table (DESIGN.md §9 "The launch path"): what a launch stages and which instantiation runs, decided
+// once.  Shape says what the kernel does with the scene; kernel_of maps (form, family, shape) to the instantiation
+// and its block size.  The attribute check, the occupancy queries, the launch and the diagnostics
+// (rt_nw_ctx_last_kernel, rt_nw_ctx_last_staging) all read these two, so they cannot disagree.
+// ---------------------------------------------------------------------------
+struct Shape {
+  bool persist = false;    // the persistent kernels (one launch-long block per resident slot), else one wave per item
+  bool grid = false;       // the uniform grid, staged whole (objects, cells, brute-force list), else the BVH
+  bool simple = false;     // ... its spheres-only instantiation (persistent only)
+  bool lds_nodes = false;  // BVH: the nodes are staged (the persistent kernels always stage them)
+  bool lds_objs = false;   // BVH: ... and the objects beside them
+  size_t lds = 0;          // the dynamic LDS bytes that go with the flags above
+};
+
+// The form of a launch: the kernel writes the floats itself (all samples of a tile in one item), adds fixed-point
+// sums into an accumulator, or is the adaptive twin (which always adds).
+enum Form { kOneShot, kChunked, kAdapt, kForms };
+constexpr int kFamilies = 6;  // the kernels' TRI, rt_nw_ctx::has_tri
+
+struct Kernel {
+  const void *fn;
+  int waves;  // per block
+};
+
+// The only place that names the render kernels.  T < 3: the families that may have a grid.
+template <Form F, int T> Kernel kernel_ft(const Shape &s) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  auto persistent = [](auto objs, auto grid, auto simple) -> const void * {
+    constexpr bool O = decltype(objs)::value, G = decltype(grid)::value, S = decltype(simple)::value;
+    constexpr int TT = S ? 0 : T;  // (a spheres-only scene holds no triangle)
+    if constexpr (F == kAdapt) return (const void *)render_persistent_adapt<O, G, S, TT>;
+    else return (const void *)render_persistent<F == kChunked, O, G, S, TT>;
+  };
+  auto one_shot = [](auto nodes, auto objs, auto grid) -> const void * {
+    constexpr bool Nd = decltype(nodes)::value, O = decltype(objs)::value, G = decltype(grid)::value;
+    if constexpr (F == kAdapt) return (const void *)render_kernel_adapt<Nd, O, G, T>;
+    else return (const void *)render_kernel<F == kChunked, Nd, O, G, T>;
+  };
+  if constexpr (T < 3) {
+    if (s.simple) return {persistent(Y{}, Y{}, Y{}), persist_waves<true>()};
+    if (s.grid) return s.persist ? Kernel{persistent(Y{}, Y{}, N{}), kPWaves} : Kernel{one_shot(N{}, N{}, Y{}), kWaves};
+  }
+  if (s.persist) return {s.lds_objs ? persistent(Y{}, N{}, N{}) : persistent(N{}, N{}, N{}), kPWaves};
+  return {s.lds_objs ? one_shot(Y{}, Y{}, N{}) : s.lds_nodes ? one_shot(Y{}, N{}, N{}) : one_shot(N{}, N{}, N{}), kWaves};
+}
+
+Kernel kernel_of(Form form, int tri, const Shape &s) {
+  using Fn = Kernel (*)(const Shape &);
+#define RTMI_NW_FAMILIES(F) {kernel_ft<F, 0>, kernel_ft<F, 1>, kernel_ft<F, 2>, kernel_ft<F, 3>, kernel_ft<F, 4>, kernel_ft<F, 5>}
+  static constexpr Fn table[kForms][kFamilies] = {RTMI_NW_FAMILIES(kOneShot), RTMI_NW_FAMILIES(kChunked), RTMI_NW_FAMILIES(kAdapt)};
+#undef RTMI_NW_FAMILIES
+  return table[form][tri](s);
+}
+
+// resident blocks per CU of a persistent kernel that stages nothing yet (rt_nw_ctx_create)
+int blocks_per_cu(const Shape &s, int *per_cu) {
+  const Kernel k = kernel_of(kChunked, 0, s);
+  *per_cu = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k.fn, 64 * k.waves, 0));
+  return RT_OK;
+}
+
 }  // namespace
 
 RTMI_EXPORT int rt_nw_ctx_create(int32_t device, rt_nw_ctx **out) {
@@ -977,18 +1011,19 @@ RTMI_EXPORT int rt_nw_ctx_create(int32_t device, rt_nw_ctx **out) {
   if (int rc = alloc_copy<unsigned long long>(&ctx->segments, nullptr, 1)) return rc;
   HIP_TRY(hipMemset(ctx->segments, 0, sizeof(unsigned long long)));
   if (int rc = alloc_copy<unsigned>(&ctx->counter, nullptr, 1)) return rc;
-  {
-    int per_cu = 0;  // the persistent grid: what stays resident (VGPR-limited: one 16-wave block per CU)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)render_persistent<true, false, false>,
-                                                         64 * kPWaves, 0));
+  {  // what stays resident of the persistent kernels (VGPR-limited: one 16-wave block per CU): the BVH shape that
+     // stages the nodes alone, the general grid shape and its spheres-only instantiation
+    Shape s;
+    s.persist = s.lds_nodes = true;
+    int per_cu = 0;
+    if (int rc = blocks_per_cu(s, &per_cu)) return rc;
     ctx->persist_blocks = per_cu * prop.multiProcessorCount;
-    per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)render_persistent<true, true, true>,
-                                                         64 * kPWaves, 0));
+    s.grid = true;
+    s.lds_nodes = false;
+    if (int rc = blocks_per_cu(s, &per_cu)) return rc;
     ctx->persist_blocks_grid = per_cu * prop.multiProcessorCount;
-    per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)render_persistent<true, true, true, true>,
-                                                         64 * persist_waves<true>(), 0));
+    s.simple = true;
+    if (int rc = blocks_per_cu(s, &per_cu)) return rc;
     ctx->persist_blocks_simple = per_cu * prop.multiProcessorCount;
     ctx->cus = prop.multiProcessorCount;
   }
@@ -997,21 +1032,7 @@ RTMI_EXPORT int rt_nw_ctx_create(int32_t device, rt_nw_ctx **out) {
 }
 
 RTMI_EXPORT int rt_nw_ctx_destroy(rt_nw_ctx *ctx) {
-  if (!ctx) return RT_OK;
-  Guard g(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (void *p : {(void *)ctx->obj, (void *)ctx->obj_id, (void *)ctx->med, (void *)ctx->med_id, (void *)ctx->inst, (void *)ctx->mat, (void *)ctx->tex,
-                  (void *)ctx->pvec, (void *)ctx->pperm, (void *)ctx->img, (void *)ctx->imgd, (void *)ctx->nodes,
-                  (void *)ctx->accum, (void *)ctx->scratch, (void *)ctx->segments, (void *)ctx->counter,
-                  (void *)ctx->grid_cells, (void *)ctx->grid_refs, (void *)ctx->grid_big, (void *)ctx->pass_accum,
-                  (void *)ctx->adapt_sum, (void *)ctx->adapt_m2, (void *)ctx->adapt_n, (void *)ctx->adapt_list[0].tiles,
-                  (void *)ctx->adapt_list[0].masks, (void *)ctx->adapt_list[1].tiles, (void *)ctx->adapt_list[1].masks})
-    if (p) (void)hipFree(p);
-  for (auto &l : ctx->adapt_list)
-    if (l.done) (void)hipEventDestroy(l.done);
-  (void)hipStreamDestroy(ctx->stream);
-  if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
-  delete ctx;
+  delete ctx;  // (~rt_nw_ctx)
   return RT_OK;
 }
 
@@ -1279,12 +1300,13 @@ constexpr int32_t kNwGridMaxCell = 24;  // AUTO: a grid with a fuller cell rende
 size_t grid_bytes(const rt_nw_ctx *c) {
   return nw_grid_lds_bytes(c->nobj, c->grid.ncells, c->grid.nrefs, c->nbig);
 }
+// a grid renders with the persistent kernel
+bool grid_persists(const rt_nw_ctx *c) { return RTMI_NW_PERSIST && c->persist_ok && c->persist_blocks_grid > 0; }
 int32_t accel_used(const rt_nw_ctx *c) {
   // the grid is staged whole: by the persistent kernel (one block per CU)
   // when it runs, else by the grid kernel's per-block budget; a grid that
   // fits neither renders with the BVH
-  const bool persist = RTMI_NW_PERSIST && c->persist_ok && c->persist_blocks_grid > 0;
-  const bool fits = c->grid_ok && grid_bytes(c) <= (persist ? kPLdsBudget : kLdsBudget);
+  const bool fits = c->grid_ok && grid_bytes(c) <= (grid_persists(c) ? kPLdsBudget : kLdsBudget);
   if (c->accel == RT_NW_ACCEL_GRID) return fits ? RT_NW_ACCEL_GRID : RT_NW_ACCEL_BVH;
   if (c->accel == RT_NW_ACCEL_BVH) return RT_NW_ACCEL_BVH;
   return fits && c->grid_max_cell <= kNwGridMaxCell ? RT_NW_ACCEL_GRID : RT_NW_ACCEL_BVH;
@@ -1329,6 +1351,56 @@ int check_rows_args(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t 
   return RT_OK;
 }
 
+// The shape of a launch of the context's scene, plain or adaptive.  The adaptive kernels' static LDS is larger, so
+// they have staging budgets of their own, and a grid that fits the plain kernels' budget but not theirs is walked
+// as a BVH by an adaptive pass (the same image).
+int shape_of(const rt_nw_ctx *ctx, bool adapt, Shape &s) {
+  const size_t p_budget = adapt ? kPLdsBudgetA : kPLdsBudget, p_two_budget = adapt ? kPTwoBlockBudgetA : kPTwoBlockBudget,
+               g_budget = adapt ? kLdsBudgetA : kLdsBudget;
+  const size_t node_bytes = size_t(ctx->nnodes) * 32, obj_bytes = size_t(ctx->nobj) * (sizeof(DevObj) + 4);
+  s = Shape{};
+  s.grid = accel_used(ctx) == RT_NW_ACCEL_GRID && (!adapt || grid_bytes(ctx) <= (grid_persists(ctx) ? p_budget : g_budget));
+  // persistent when the grid, or the nodes, fit one CU's LDS budget; else one wave per work item
+  s.persist = RTMI_NW_PERSIST && ctx->persist_ok && (s.grid ? ctx->persist_blocks_grid > 0 : ctx->persist_blocks > 0) &&
+              (s.grid || (ctx->nnodes > 0 && node_bytes <= p_budget));
+  if (s.grid) {
+    s.lds = grid_bytes(ctx);
+    if (!s.persist && s.lds > g_budget) return set_error(RT_EINVAL, "rt_nw: grid does not fit the grid kernel's LDS");
+    if (ctx->has_tri >= 3) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
+    s.simple = s.persist && ctx->simple && ctx->simple_ok && ctx->persist_blocks_simple > 0;
+    return RT_OK;
+  }
+  if (s.persist) {
+    // objects staged beside the nodes only when two blocks still fit a CU (or
+    // when one block per CU is all the nodes allow anyway)
+    // (the two-level kernels below 8 waves per SIMD run one block per CU whatever they stage)
+    const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8) ||
+                           (ctx->has_tri == 5 && RTMI_NW_AFFINE_PER_EU < 8);
+    s.lds_nodes = true;
+    s.lds_objs = RTMI_NW_LDS_OBJS && (node_bytes + obj_bytes <= p_two_budget ||
+                                      ((one_block || node_bytes > p_two_budget) && node_bytes + obj_bytes <= p_budget));
+  } else {  // per block: the nodes when they fit, then the objects too
+    s.lds_nodes = ctx->nnodes > 0 && node_bytes <= g_budget;
+    s.lds_objs = RTMI_NW_LDS_OBJS && s.lds_nodes && node_bytes + obj_bytes <= g_budget;
+  }
+  s.lds = s.lds_nodes ? node_bytes + (s.lds_objs ? obj_bytes : 0) : 0;
+  return RT_OK;
+}
+
+// The context's buffers (accumulators, counters, scratch) are shared by everything it launches: work on another
+// stream first waits for the end of the last one ...
+int take_turn(rt_nw_ctx *ctx, hipStream_t st) {
+  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
+  ctx->last_stream = st;
+  return RT_OK;
+}
+// ... and records its own end, whatever path returns
+struct MarkDone {
+  rt_nw_ctx *c;
+  hipStream_t s;
+  ~MarkDone() { (void)hipEventRecord(c->last_done, s); }
+};
+
 // With adapt set (rt_nw_adapt_pass): pass_accum is the adaptive accumulator's sums, the work items cover the listed
 // tiles only, each active pixel p takes the samples n[p] + [0, spp), and the ADAPT twin of the same shape runs.
 struct AdaptLaunch {
@@ -1344,139 +1416,53 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   const int32_t valid = std::min<int64_t>(nrows, (int64_t(H) - 1 - row0) / row_step + 1);
   Guard g(ctx->device);
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  Args a;
-  a.cam = camf(cam->cam);
-  a.time0 = float(cam->time0);
-  a.time1 = float(cam->time1);
-  a.W = W;
-  a.H = H;
+  Args a = camera_args(cam, W, H, max_depth, seed);
   a.s_end = s_base + spp;
   a.s_base = s_base;
-  a.max_depth = max_depth;
-  a.seed = seed;
   a.row0 = row0;
   a.row_step = row_step;
   a.nrows_valid = valid;
   a.tiles_x = (W + 7) / 8;
   a.tiles = adapt ? adapt->n_tiles : a.tiles_x * ((valid + 7) / 8);
-  // the adaptive kernels' static LDS is larger: staging budgets of their own
-  const size_t p_budget = adapt ? kPLdsBudgetA : kPLdsBudget, p_two_budget = adapt ? kPTwoBlockBudgetA : kPTwoBlockBudget,
-               g_budget = adapt ? kLdsBudgetA : kLdsBudget;
-  // kernel shape: persistent when the nodes fit one CU's LDS budget, else grid
-  const size_t node_bytes = size_t(ctx->nnodes) * 32, obj_bytes = size_t(ctx->nobj) * (sizeof(DevObj) + 4);
-  // (an adaptive pass of a grid that fits the plain kernels' budget but not its own walks the BVH: the same image)
-  const bool want_persist = RTMI_NW_PERSIST && ctx->persist_ok && ctx->persist_blocks_grid > 0;
-  const bool use_grid = accel_used(ctx) == RT_NW_ACCEL_GRID && (!adapt || grid_bytes(ctx) <= (want_persist ? p_budget : g_budget));
-  const size_t gbytes = use_grid ? grid_bytes(ctx) : 0;
-  const bool persist = RTMI_NW_PERSIST && ctx->persist_ok && (use_grid ? ctx->persist_blocks_grid > 0 : ctx->persist_blocks > 0) &&
-                       (use_grid || (ctx->nnodes > 0 && node_bytes <= p_budget));
-  // the spheres-only instantiation of the persistent grid kernel
-  const bool simple = persist && use_grid && ctx->simple && ctx->simple_ok && ctx->persist_blocks_simple > 0;
-  const int32_t pblocks = simple ? ctx->persist_blocks_simple : use_grid ? ctx->persist_blocks_grid : ctx->persist_blocks;
-  const int64_t pwaves = simple ? persist_waves<true>() : kPWaves;
+  Shape sh;
+  if (int rc = shape_of(ctx, adapt != nullptr, sh)) return rc;
+  // The kernel that is asked about (its static LDS, how many of its blocks stay resident) is the accumulating
+  // instantiation even when the float-writing one launches below: the two of a shape have equal VGPR, SGPR and
+  // LDS figures (profiles/adaptive/kernel_resources.txt), and the answer is needed before the launch knows
+  // whether one work item per tile is enough.
+  const Form asked = adapt ? kAdapt : kChunked;
+  const Kernel ask = kernel_of(asked, ctx->has_tri, sh);
+  if (int rc = take_turn(ctx, st)) return rc;
+  MarkDone mark_done{ctx, st};
+  if (valid < nrows && !pass_accum)  // rows past H: zero (a pass leaves them as rt_nw_accum_reset zeroed them)
+    HIP_TRY(hipMemsetAsync(dev_strip + size_t(valid) * W * 3, 0, size_t(nrows - valid) * W * 3 * sizeof(float), st));
+  HIP_TRY(hipMemsetAsync(ctx->segments, 0, sizeof(unsigned long long), st));
+  {
+    hipFuncAttributes fa;
+    HIP_TRY(hipFuncGetAttributes(&fa, ask.fn));
+    if (fa.sharedSizeBytes + sh.lds > kCuLds)
+      return set_error(RT_EINVAL, "rt_nw: %zu B staged + %zu B static LDS exceed a CU's %zu B", sh.lds,
+                       size_t(fa.sharedSizeBytes), kCuLds);
+  }
   // samples per work item (same image for any size; RTMI_NW_CHUNK overrides,
   // for A/B).  Persistent kernel: ~80 items per resident wave, 4..32 samples:
   // the final scene (fog, lights: long and uneven paths) at 256 spp runs 329
   // ms with 8, 433 with 32; at 1024 spp 1215 ms with 24, 1205 with 32, 1308
   // with 8 — the item count, not the size, sets its tail
   // (profiles/r01/session6/nw_chunk.txt).  Grid kernel: 32.
-  // (samples per work item: set below, once the resident grid is known)
-  // the context's buffers (accumulator, counters) are shared by every render:
-  // a render on another stream first waits for the last one
-  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
-  ctx->last_stream = st;
-  struct MarkDone {  // record the end of this render's work, whatever path returns
-    rt_nw_ctx *c;
-    hipStream_t s;
-    ~MarkDone() { (void)hipEventRecord(c->last_done, s); }
-  } mark_done{ctx, st};
-  if (valid < nrows && !pass_accum)  // rows past H: zero (a pass leaves them as rt_nw_accum_reset zeroed them)
-    HIP_TRY(hipMemsetAsync(dev_strip + size_t(valid) * W * 3, 0, size_t(nrows - valid) * W * 3 * sizeof(float), st));
-  HIP_TRY(hipMemsetAsync(ctx->segments, 0, sizeof(unsigned long long), st));
-  const View v = view_of(ctx);
-  // objects staged beside the nodes only when two blocks still fit a CU (or
-  // when one block per CU is all the nodes allow anyway)
-  // (the two-level kernels below 8 waves per SIMD run one block per CU whatever they stage)
-  const bool one_block = (ctx->has_tri == 3 && RTMI_NW_INST_PER_EU < 8) || (ctx->has_tri == 4 && RTMI_NW_MOVE_PER_EU < 8) ||
-                         (ctx->has_tri == 5 && RTMI_NW_AFFINE_PER_EU < 8);
-  const bool p_objs = RTMI_NW_LDS_OBJS && persist &&
-                      (node_bytes + obj_bytes <= p_two_budget ||
-                       ((one_block || node_bytes > p_two_budget) && node_bytes + obj_bytes <= p_budget));
-  const bool g_grid = use_grid && !persist && gbytes <= g_budget;  // grid kernel with the grid staged per block
-  if (use_grid && !persist && !g_grid) return set_error(RT_EINVAL, "rt_nw: grid does not fit the grid kernel's LDS");
-  const bool lds_nodes = !persist && !use_grid && ctx->nnodes > 0 && node_bytes <= g_budget,
-             lds_objs = RTMI_NW_LDS_OBJS && lds_nodes && node_bytes + obj_bytes <= g_budget;
-  const size_t lds = use_grid ? gbytes
-                     : persist ? (p_objs ? node_bytes + obj_bytes : node_bytes)
-                               : lds_objs ? node_bytes + obj_bytes : lds_nodes ? node_bytes : 0;
-  // the kernel that will run, its static LDS beside the staged bytes, and
-  // (persistent) how many of its blocks stay resident with those bytes
-  auto kernel_of = [&](auto tri) -> const void * {
-    constexpr int T = decltype(tri)::value;
-    if (adapt) {  // the twin of the same shape
-      if constexpr (T < 3) {
-        if (simple) return (const void *)render_persistent_adapt<true, true, true>;
-        if (persist && use_grid) return (const void *)render_persistent_adapt<true, true, false, T>;
-        if (g_grid) return (const void *)render_kernel_adapt<false, false, true, T>;
-      }
-      return persist && p_objs ? (const void *)render_persistent_adapt<true, false, false, T>
-             : persist         ? (const void *)render_persistent_adapt<false, false, false, T>
-             : lds_objs        ? (const void *)render_kernel_adapt<true, true, false, T>
-             : lds_nodes       ? (const void *)render_kernel_adapt<true, false, false, T>
-                               : (const void *)render_kernel_adapt<false, false, false, T>;
-    }
-    if constexpr (T >= 3)  // (BVH shapes only)
-      return persist && p_objs ? (const void *)render_persistent<true, true, false, false, T>
-             : persist         ? (const void *)render_persistent<true, false, false, false, T>
-             : lds_objs        ? (const void *)render_kernel<true, true, true, false, T>
-             : lds_nodes       ? (const void *)render_kernel<true, true, false, false, T>
-                               : (const void *)render_kernel<true, false, false, false, T>;
-    else
-      return simple                ? (const void *)render_persistent<true, true, true, true>
-             : persist && use_grid ? (const void *)render_persistent<true, true, true, false, T>
-             : persist && p_objs   ? (const void *)render_persistent<true, true, false, false, T>
-             : persist             ? (const void *)render_persistent<true, false, false, false, T>
-             : g_grid              ? (const void *)render_kernel<true, false, false, true, T>
-             : lds_objs            ? (const void *)render_kernel<true, true, true, false, T>
-             : lds_nodes           ? (const void *)render_kernel<true, true, false, false, T>
-                                   : (const void *)render_kernel<true, false, false, false, T>;
-  };
-  using Tri0 = std::integral_constant<int, 0>;
-  using Tri1 = std::integral_constant<int, 1>;
-  using Tri2 = std::integral_constant<int, 2>;
-  using Tri3 = std::integral_constant<int, 3>;
-  using Tri4 = std::integral_constant<int, 4>;
-  using Tri5 = std::integral_constant<int, 5>;
-  if (ctx->has_tri >= 3 && use_grid) return set_error(RT_EINVAL, "rt_nw: a scene with placements has no grid");
-  const void *kfn = ctx->has_tri == 5   ? kernel_of(Tri5{})
-                    : ctx->has_tri == 4 ? kernel_of(Tri4{})
-                    : ctx->has_tri == 3 ? kernel_of(Tri3{})
-                    : ctx->has_tri == 2 ? kernel_of(Tri2{})
-                    : ctx->has_tri      ? kernel_of(Tri1{})
-                                        : kernel_of(Tri0{});
-  {
-    hipFuncAttributes fa;
-    HIP_TRY(hipFuncGetAttributes(&fa, kfn));
-    if (fa.sharedSizeBytes + lds > kCuLds)
-      return set_error(RT_EINVAL, "rt_nw: %zu B staged + %zu B static LDS exceed a CU's %zu B", lds,
-                       size_t(fa.sharedSizeBytes), kCuLds);
-  }
-  int32_t resident = pblocks;
-  if (persist) {
-    const auto key = std::make_pair(kfn, lds);
+  int64_t chunk = 32;
+  int32_t resident = 0;  // persistent: the blocks that stay resident with the staged bytes
+  if (sh.persist) {
+    const auto key = std::make_pair(ask.fn, sh.lds);
     auto it = std::find_if(ctx->occupancy.begin(), ctx->occupancy.end(), [&](const auto &e) { return e.first == key; });
     if (it == ctx->occupancy.end()) {
       int per_cu = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, int(64 * pwaves), lds));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ask.fn, 64 * ask.waves, sh.lds));
       ctx->occupancy.push_back({key, std::max(1, per_cu) * ctx->cus});
       it = ctx->occupancy.end() - 1;
     }
     resident = it->second;
-  }
-  int64_t chunk = 32;
-  if (persist) {
-    const int64_t waves = int64_t(resident) * pwaves;
-    chunk = std::min<int64_t>(32, std::max<int64_t>(4, int64_t(a.tiles) * spp / (80 * waves)));
+    chunk = std::min<int64_t>(32, std::max<int64_t>(4, int64_t(a.tiles) * spp / (80 * int64_t(resident) * ask.waves)));
   }
   // (at most 65535 samples per item: job indices stay below 2^22, where the
   // kernels' reciprocal-multiply job decode is exact)
@@ -1484,87 +1470,21 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
   a.nch = (spp + a.chunk - 1) / a.chunk;
   if (int64_t(a.tiles) * a.nch >= (int64_t(1) << 31) - kWaves) return set_error(RT_EINVAL, "render too large");
   a.n_items = a.tiles * a.nch;
-  const unsigned blocks = persist ? unsigned(std::min<int64_t>(resident, (a.n_items + pwaves - 1) / pwaves))
-                                  : unsigned((a.n_items + kWaves - 1) / kWaves);
-  if (persist) HIP_TRY(hipMemsetAsync(ctx->counter, 0, sizeof(unsigned), st));
-  ctx->last_kernel[0] = persist ? 1 : 0;
-  ctx->last_kernel[1] = use_grid ? 1 : 0;
-  ctx->last_kernel[2] = simple ? 1 : 0;
+  const unsigned blocks = unsigned(sh.persist ? std::min<int64_t>(resident, (a.n_items + ask.waves - 1) / ask.waves)
+                                              : (a.n_items + kWaves - 1) / kWaves);
+  if (sh.persist) HIP_TRY(hipMemsetAsync(ctx->counter, 0, sizeof(unsigned), st));
+  ctx->last_kernel[0] = sh.persist ? 1 : 0;
+  ctx->last_kernel[1] = sh.grid ? 1 : 0;
+  ctx->last_kernel[2] = sh.simple ? 1 : 0;
   ctx->last_kernel[3] = a.chunk;
-  ctx->last_staging[0] = !use_grid && (persist || lds_nodes) ? 1 : 0;
-  ctx->last_staging[1] = use_grid || (persist ? p_objs : lds_objs) ? 1 : 0;
-  // (a pass adds into its own accumulator; ctx->accum stays the per-render scratch, sized below)
+  ctx->last_staging[0] = sh.lds_nodes ? 1 : 0;
+  ctx->last_staging[1] = sh.grid || sh.lds_objs ? 1 : 0;
+  // A pass adds into its own accumulator, whatever nch is: no memset, no finalize (rt_nw_accum_resolve).  A render
+  // of several items per tile adds into ctx->accum, the per-render scratch; one item per tile writes the floats.
   unsigned long long *acc_buf = pass_accum;
-  auto launch_t = [&](auto chunked, auto tri) {
-    constexpr bool C = decltype(chunked)::value;
-    constexpr int T = decltype(tri)::value;
-    if constexpr (C) {
-      if (adapt) {
-        const AdaptArgs &ad = adapt->dev;
-        if constexpr (T < 3) {
-          if (simple) {
-            hipLaunchKernelGGL((render_persistent_adapt<true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
-            return;
-          }
-          if (persist && use_grid) {
-            hipLaunchKernelGGL((render_persistent_adapt<true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
-            return;
-          }
-          if (!persist && g_grid) {
-            hipLaunchKernelGGL((render_kernel_adapt<false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
-            return;
-          }
-        }
-        if (persist && p_objs)
-          hipLaunchKernelGGL((render_persistent_adapt<true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
-        else if (persist)
-          hipLaunchKernelGGL((render_persistent_adapt<false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, ad, acc_buf, ctx->segments, ctx->counter);
-        else if (lds_objs)
-          hipLaunchKernelGGL((render_kernel_adapt<true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
-        else if (lds_nodes)
-          hipLaunchKernelGGL((render_kernel_adapt<true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, ad, acc_buf, ctx->segments);
-        else
-          hipLaunchKernelGGL((render_kernel_adapt<false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, ad, acc_buf, ctx->segments);
-        return;
-      }
-    }
-    if constexpr (T < 3) {  // (a scene with placements has no grid)
-      if (simple) {
-        hipLaunchKernelGGL((render_persistent<C, true, true, true>), dim3(blocks), dim3(64 * persist_waves<true>()), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
-        return;
-      }
-      if (persist && use_grid) {
-        hipLaunchKernelGGL((render_persistent<C, true, true, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
-        return;
-      }
-      if (!persist && g_grid) {
-        hipLaunchKernelGGL((render_kernel<C, false, false, true, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
-        return;
-      }
-    }
-    if (persist && p_objs)
-      hipLaunchKernelGGL((render_persistent<C, true, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
-    else if (persist)
-      hipLaunchKernelGGL((render_persistent<C, false, false, false, T>), dim3(blocks), dim3(64 * kPWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments, ctx->counter);
-    else if (lds_objs)
-      hipLaunchKernelGGL((render_kernel<C, true, true, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
-    else if (lds_nodes)
-      hipLaunchKernelGGL((render_kernel<C, true, false, false, T>), dim3(blocks), dim3(64 * kWaves), lds, st, v, a, acc_buf, dev_strip, ctx->segments);
-    else
-      hipLaunchKernelGGL((render_kernel<C, false, false, false, T>), dim3(blocks), dim3(64 * kWaves), 0, st, v, a, acc_buf, dev_strip, ctx->segments);
-  };
-  auto launch = [&](auto chunked) {
-    if (ctx->has_tri == 5) launch_t(chunked, Tri5{});
-    else if (ctx->has_tri == 4) launch_t(chunked, Tri4{});
-    else if (ctx->has_tri == 3) launch_t(chunked, Tri3{});
-    else if (ctx->has_tri == 2) launch_t(chunked, Tri2{});
-    else if (ctx->has_tri) launch_t(chunked, Tri1{});
-    else launch_t(chunked, Tri0{});
-  };
-  if (pass_accum) {  // chunked whatever nch is: no memset, no finalize (rt_nw_accum_resolve)
-    launch(std::true_type{});
-  } else if (a.nch > 1) {
-    const size_t nv = size_t(valid) * W * 3;
+  const size_t nv = size_t(valid) * W * 3;
+  const bool scratch = !pass_accum && a.nch > 1;
+  if (scratch) {
     if (nv > ctx->accum_cap) {
       HIP_TRY(hipStreamSynchronize(st));
       if (int rc = alloc_copy<unsigned long long>(&ctx->accum, nullptr, nv)) return rc;
@@ -1572,13 +1492,18 @@ int render_rows_impl(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t
     }
     HIP_TRY(hipMemsetAsync(ctx->accum, 0, nv * sizeof(unsigned long long), st));
     acc_buf = ctx->accum;
-    launch(std::true_type{});
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(finalize_kernel, dim3(unsigned((nv + 255) / 256)), dim3(256), 0, st, ctx->accum, dev_strip, nv);
-  } else {
-    launch(std::false_type{});
   }
-  HIP_TRY(hipGetLastError());
+  const Kernel k = kernel_of(pass_accum || scratch ? asked : kOneShot, ctx->has_tri, sh);
+  View v = view_of(ctx);
+  AdaptArgs ad = adapt ? adapt->dev : AdaptArgs{};
+  // View, Args, [AdaptArgs,] accum, [out,] segments [, counter]
+  void *args[6] = {&v, &a, adapt ? (void *)&ad : (void *)&acc_buf, adapt ? (void *)&acc_buf : (void *)&dev_strip, &ctx->segments,
+                   &ctx->counter};
+  HIP_TRY(hipLaunchKernel(k.fn, dim3(blocks), dim3(64 * k.waves), args, sh.lds, st));
+  if (scratch) {
+    hipLaunchKernelGGL(finalize_kernel, dim3(unsigned((nv + 255) / 256)), dim3(256), 0, st, ctx->accum, dev_strip, nv);
+    HIP_TRY(hipGetLastError());
+  }
   return RT_OK;
 }
 }  // namespace
@@ -1676,8 +1601,7 @@ RTMI_EXPORT int rt_nw_accum_resolve(rt_nw_ctx *ctx, float *dev_sum, float *host_
   }
   // a resolve on another stream waits for the last pass (and, as it may write the shared scratch, it is
   // itself work the next render waits for)
-  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
-  ctx->last_stream = st;
+  if (int rc = take_turn(ctx, st)) return rc;
   hipLaunchKernelGGL(finalize_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, ctx->pass_accum, out, n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && host_sum) e = hipMemcpyAsync(host_sum, out, n * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1840,10 +1764,9 @@ RTMI_EXPORT int rt_nw_adapt_pass(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_
   Guard g(ctx->device);
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if (tiles.empty()) {  // nothing to sample: no launch, a count of zero segments
-    if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
-    ctx->last_stream = st;
+    if (int rc = take_turn(ctx, st)) return rc;
+    MarkDone mark_done{ctx, st};
     HIP_TRY(hipMemsetAsync(ctx->segments, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipEventRecord(ctx->last_done, st));
     return RT_OK;
   }
   // the list goes into the slot the pass before the last one used (that pass has to have ended: the host waits for
@@ -1939,8 +1862,7 @@ RTMI_EXPORT int rt_nw_adapt_resolve(rt_nw_ctx *ctx, float *dev_mean, float *host
     }
     out = ctx->scratch;
   }
-  if (ctx->last_stream && ctx->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, ctx->last_done, 0));
-  ctx->last_stream = st;
+  if (int rc = take_turn(ctx, st)) return rc;
   hipLaunchKernelGGL(adapt_resolve_kernel, dim3(unsigned((npix + 255) / 256)), dim3(256), 0, st, ctx->adapt_sum, ctx->adapt_n, out,
                      npix);
   hipError_t e = hipGetLastError();
@@ -2089,37 +2011,74 @@ RTMI_EXPORT int rt_nw_render_adaptive(rt_nw_ctx *ctx, rt_nw_scene *scene, const 
   return RT_OK;
 }
 
+namespace {
+// The validation kernels by walk (enum Walk), and the walk of the context's scene: its family's two-level walk,
+// else the grid where the renders use it (grid), else the BVH.  A trace always walks the BVH.
+const void *const kTraceKernels[kWalks] = {(const void *)trace_kernel<kWalkBvh>, nullptr, (const void *)trace_kernel<kWalkInst>,
+                                           (const void *)trace_kernel<kWalkMove>, (const void *)trace_kernel<kWalkAffine>};
+const void *const kHitsKernels[kWalks] = {(const void *)debug_hits_kernel<kWalkBvh>, (const void *)debug_hits_kernel<kWalkGrid>,
+                                          (const void *)debug_hits_kernel<kWalkInst>, (const void *)debug_hits_kernel<kWalkMove>,
+                                          (const void *)debug_hits_kernel<kWalkAffine>};
+const void *const kRecordsKernels[kWalks] = {(const void *)debug_records_kernel<kWalkBvh>, (const void *)debug_records_kernel<kWalkGrid>,
+                                             (const void *)debug_records_kernel<kWalkInst>, (const void *)debug_records_kernel<kWalkMove>,
+                                             (const void *)debug_records_kernel<kWalkAffine>};
+int walk_of(const rt_nw_ctx *ctx, bool grid) { return ctx->has_tri >= 3 ? kWalkInst + (ctx->has_tri - 3) : grid ? kWalkGrid : kWalkBvh; }
+
+// rt_nw_debug_hits and rt_nw_debug_records (records): the rays up, one launch through the scene's walk, the results
+// down.  out_aux: the box faces or the materials; out_pnuv: records only.
+int debug_rays(rt_nw_ctx *ctx, const char *who, bool records, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
+               float *out_t, int32_t *out_aux, float *out_pnuv) {
+  if (!ctx || (n > 0 && (!rays || !out_id || !out_t || !out_aux || (records && !out_pnuv))) || n < 0)
+    return set_error(RT_EINVAL, "%s: bad argument", who);
+  if (ctx->nobj + ctx->nmed <= 0) return set_error(RT_EINVAL, "no scene uploaded (rt_nw_ctx_set_scene)");
+  if (n == 0) return RT_OK;
+  Guard g(ctx->device);
+  const bool grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
+  const size_t lds = grid ? grid_bytes(ctx) : 0, count = size_t(n);
+  if (lds > kCuLds) return set_error(RT_EUNSUPPORTED, "%s: grid of %zu B exceeds a CU's LDS", who, lds);
+  DevBuf<float> d_rays, d_t, d_pnuv;
+  DevBuf<unsigned long long> d_keys;
+  DevBuf<int32_t> d_id, d_aux;
+  hipError_t e = d_rays.upload(rays, count * 8);
+  if (e == hipSuccess && keys) e = d_keys.upload(reinterpret_cast<const unsigned long long *>(keys), count);
+  if (e == hipSuccess) e = d_t.alloc(count);
+  if (e == hipSuccess) e = d_id.alloc(count);
+  if (e == hipSuccess) e = d_aux.alloc(count);
+  if (e == hipSuccess && records) e = d_pnuv.alloc(count * 8);
+  if (e == hipSuccess) {
+    View v = view_of(ctx);
+    DebugRays q{d_rays.p, d_keys.p, n, ctx->nattr > 0 ? 1 : 0, d_id.p, d_t.p, d_aux.p, d_pnuv.p};
+    void *args[] = {&v, &q};
+    e = hipLaunchKernel((records ? kRecordsKernels : kHitsKernels)[walk_of(ctx, grid)], dim3(unsigned((n + 255) / 256)), dim3(256),
+                        args, lds, ctx->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = d_id.download(out_id, count);
+  if (e == hipSuccess) e = d_t.download(out_t, count);
+  if (e == hipSuccess) e = d_aux.download(out_aux, count);
+  if (e == hipSuccess && records) e = d_pnuv.download(out_pnuv, count * 8);
+  if (e != hipSuccess) return set_error(RT_EHIP, "%s: %s", who, hipGetErrorString(e));
+  return RT_OK;
+}
+}  // namespace
+
 RTMI_EXPORT int rt_nw_debug_trace(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t max_depth,
                                   uint64_t seed, int32_t i, int32_t j, int32_t s, float *rec, int32_t cap, int32_t *n) {
   if (!ctx || !cam || !rec || !n || cap < 1 || max_depth < 1 || i < 0 || i >= W || j < 0 || j >= H)
     return set_error(RT_EINVAL, "rt_nw_debug_trace: bad argument");
   Guard g(ctx->device);
-  Args a{};
-  a.cam = camf(cam->cam);
-  a.time0 = float(cam->time0);
-  a.time1 = float(cam->time1);
-  a.W = W;
-  a.H = H;
-  a.max_depth = max_depth;
-  a.seed = seed;
-  float *d_rec = nullptr;
-  int *d_n = nullptr;
-  HIP_TRY(hipMalloc(&d_rec, size_t(cap) * 12 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_n, sizeof(int)));
-  if (ctx->has_tri == 5)
-    hipLaunchKernelGGL(trace_affine_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
-  else if (ctx->has_tri == 4)
-    hipLaunchKernelGGL(trace_move_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
-  else if (ctx->has_tri == 3)
-    hipLaunchKernelGGL(trace_inst_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n);
-  else
-    hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(64), 0, ctx->stream, view_of(ctx), a, i, j, s, d_rec, cap, d_n,
-                       ctx->nattr > 0 ? 1 : 0);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(n, d_n, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(rec, d_rec, size_t(*n) * 12 * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_rec);
-  (void)hipFree(d_n);
+  View v = view_of(ctx);
+  Args a = camera_args(cam, W, H, max_depth, seed);
+  int has_attr = ctx->nattr > 0 ? 1 : 0;
+  DevBuf<float> d_rec;
+  DevBuf<int32_t> d_n;
+  HIP_TRY(d_rec.alloc(size_t(cap) * 12));
+  HIP_TRY(d_n.alloc(1));
+  void *args[] = {&v, &a, &i, &j, &s, &d_rec.p, &cap, &d_n.p, &has_attr};
+  hipError_t e = hipLaunchKernel(kTraceKernels[walk_of(ctx, false)], dim3(1), dim3(64), args, 0, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = d_n.download(n, 1);
+  if (e == hipSuccess) e = d_rec.download(rec, size_t(*n) * 12);
   if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_trace: %s", hipGetErrorString(e));
   return RT_OK;
 }
@@ -2130,19 +2089,11 @@ RTMI_EXPORT int rt_nw_debug_trace_t(rt_nw_ctx *ctx, const rt_nw_camera *cam, int
   if (!time) return set_error(RT_EINVAL, "rt_nw_debug_trace_t: null time");
   if (int rc = rt_nw_debug_trace(ctx, cam, W, H, max_depth, seed, i, j, s, rec, cap, n)) return rc;
   Guard g(ctx->device);
-  Args a{};
-  a.cam = camf(cam->cam);
-  a.time0 = float(cam->time0);
-  a.time1 = float(cam->time1);
-  a.W = W;
-  a.H = H;
-  a.seed = seed;
-  float *d_time = nullptr;
-  HIP_TRY(hipMalloc(&d_time, sizeof(float)));
-  hipLaunchKernelGGL(trace_time_kernel, dim3(1), dim3(64), 0, ctx->stream, a, i, j, s, d_time);
+  DevBuf<float> d_time;
+  HIP_TRY(d_time.alloc(1));
+  hipLaunchKernelGGL(trace_time_kernel, dim3(1), dim3(64), 0, ctx->stream, camera_args(cam, W, H, max_depth, seed), i, j, s, d_time.p);
   hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(time, d_time, sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_time);
+  if (e == hipSuccess) e = d_time.download(time, 1);
   if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_trace_t: %s", hipGetErrorString(e));
   return RT_OK;
 }
@@ -2155,107 +2106,12 @@ RTMI_EXPORT int rt_nw_ctx_scene_tri(rt_nw_ctx *ctx, int32_t *tri) {
 
 RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
                                  float *out_t, int32_t *out_face) {
-  if (!ctx || (n > 0 && (!rays || !out_id || !out_t || !out_face)) || n < 0)
-    return set_error(RT_EINVAL, "rt_nw_debug_hits: bad argument");
-  if (ctx->nobj + ctx->nmed <= 0) return set_error(RT_EINVAL, "no scene uploaded (rt_nw_ctx_set_scene)");
-  if (n == 0) return RT_OK;
-  Guard g(ctx->device);
-  const bool grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
-  const size_t lds = grid ? grid_bytes(ctx) : 0;
-  if (lds > kCuLds) return set_error(RT_EUNSUPPORTED, "rt_nw_debug_hits: grid of %zu B exceeds a CU's LDS", lds);
-  float *d_rays = nullptr, *d_t = nullptr;
-  unsigned long long *d_keys = nullptr;
-  int32_t *d_id = nullptr, *d_face = nullptr;
-  hipError_t e = hipMalloc(&d_rays, size_t(n) * 8 * sizeof(float));
-  if (e == hipSuccess && keys) e = hipMalloc(&d_keys, size_t(n) * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&d_t, size_t(n) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_id, size_t(n) * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_face, size_t(n) * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, size_t(n) * 8 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const dim3 grd(unsigned((n + 255) / 256)), blk(256);
-    if (ctx->has_tri == 5)
-      hipLaunchKernelGGL(debug_hits_affine_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
-    else if (ctx->has_tri == 4)
-      hipLaunchKernelGGL(debug_hits_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
-    else if (ctx->has_tri == 3)
-      hipLaunchKernelGGL(debug_hits_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_face);
-    else if (grid)
-      hipLaunchKernelGGL(debug_hits_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id,
-                         d_t, d_face);
-    else
-      hipLaunchKernelGGL(debug_hits_kernel<false>, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id,
-                         d_t, d_face);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(out_id, d_id, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_t, d_t, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_face, d_face, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d_rays);
-  (void)hipFree(d_keys);
-  (void)hipFree(d_t);
-  (void)hipFree(d_id);
-  (void)hipFree(d_face);
-  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_hits: %s", hipGetErrorString(e));
-  return RT_OK;
+  return debug_rays(ctx, "rt_nw_debug_hits", false, rays, keys, n, out_id, out_t, out_face, nullptr);
 }
 
 RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
                                     float *out_t, float *out_pnuv, int32_t *out_mat) {
-  if (!ctx || (n > 0 && (!rays || !out_id || !out_t || !out_pnuv || !out_mat)) || n < 0)
-    return set_error(RT_EINVAL, "rt_nw_debug_records: bad argument");
-  if (ctx->nobj + ctx->nmed <= 0) return set_error(RT_EINVAL, "no scene uploaded (rt_nw_ctx_set_scene)");
-  if (n == 0) return RT_OK;
-  Guard g(ctx->device);
-  const bool grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
-  const size_t lds = grid ? grid_bytes(ctx) : 0;
-  if (lds > kCuLds) return set_error(RT_EUNSUPPORTED, "rt_nw_debug_records: grid of %zu B exceeds a CU's LDS", lds);
-  float *d_rays = nullptr, *d_t = nullptr, *d_rec = nullptr;
-  unsigned long long *d_keys = nullptr;
-  int32_t *d_id = nullptr, *d_mat = nullptr;
-  hipError_t e = hipMalloc(&d_rays, size_t(n) * 8 * sizeof(float));
-  if (e == hipSuccess && keys) e = hipMalloc(&d_keys, size_t(n) * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&d_t, size_t(n) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_rec, size_t(n) * 8 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_id, size_t(n) * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_mat, size_t(n) * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, size_t(n) * 8 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && keys) e = hipMemcpy(d_keys, keys, size_t(n) * sizeof(unsigned long long), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const dim3 grd(unsigned((n + 255) / 256)), blk(256);
-    const int has_attr = ctx->nattr > 0 ? 1 : 0;
-    if (ctx->has_tri == 5)
-      hipLaunchKernelGGL(debug_records_affine_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
-                         d_mat);
-    else if (ctx->has_tri == 4)
-      hipLaunchKernelGGL(debug_records_move_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
-                         d_mat);
-    else if (ctx->has_tri == 3)
-      hipLaunchKernelGGL(debug_records_inst_kernel, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, d_id, d_t, d_rec,
-                         d_mat);
-    else if (grid)
-      hipLaunchKernelGGL(debug_records_kernel<true>, grd, blk, lds, ctx->stream, view_of(ctx), d_rays, d_keys, n, has_attr,
-                         d_id, d_t, d_rec, d_mat);
-    else
-      hipLaunchKernelGGL(debug_records_kernel<false>, grd, blk, 0, ctx->stream, view_of(ctx), d_rays, d_keys, n, has_attr,
-                         d_id, d_t, d_rec, d_mat);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(out_id, d_id, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_t, d_t, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_pnuv, d_rec, size_t(n) * 8 * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_mat, d_mat, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d_rays);
-  (void)hipFree(d_keys);
-  (void)hipFree(d_t);
-  (void)hipFree(d_rec);
-  (void)hipFree(d_id);
-  (void)hipFree(d_mat);
-  if (e != hipSuccess) return set_error(RT_EHIP, "rt_nw_debug_records: %s", hipGetErrorString(e));
-  return RT_OK;
+  return debug_rays(ctx, "rt_nw_debug_records", true, rays, keys, n, out_id, out_t, out_mat, out_pnuv);
 }
 
 // Analysis builds only (RTMI_NW_PHASES): the phase cycle sums since the last

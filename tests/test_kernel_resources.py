@@ -5,44 +5,27 @@ at most 64 VGPRs (8 waves per SIMD) and no private segment (no spills), and
 their static LDS leaves the grid's record slots room for 8 blocks per CU.
 
 The code objects are read from the library's .hip_fatbin section (clang
-offload bundles, one per linked HIP object) and their AMDGPU metadata notes
-printed by llvm-readelf."""
+offload bundles, one per linked HIP object; a_dive_into_ray_tracing_amd/codeobj.py)
+and their AMDGPU metadata notes printed by llvm-readelf."""
 import os
 import re
-import struct
 import subprocess
 
 import pytest
 
+from a_dive_into_ray_tracing_amd.codeobj import gfx950_code_objects
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "a_dive_into_ray_tracing_amd", "lib", "librtmi.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
-def gfx950_code_objects(fatbin):
-    """Every gfx950 entry of every offload bundle in the section."""
-    out, pos = [], fatbin.find(MAGIC)
-    while pos >= 0:
-        (n,) = struct.unpack_from("<Q", fatbin, pos + len(MAGIC))
-        p = pos + len(MAGIC) + 8
-        for _ in range(n):
-            off, size, tlen = struct.unpack_from("<QQQ", fatbin, p)
-            triple = fatbin[p + 24:p + 24 + tlen].decode()
-            p += 24 + tlen
-            if triple.endswith("gfx950"):
-                out.append(fatbin[pos + off:pos + off + size])
-        pos = fatbin.find(MAGIC, pos + 1)
-    return out
-
-
-def kernel_metadata(tmp_path):
-    """{kernel symbol: {field: value}} from the notes of all code objects."""
-    sec = tmp_path / "fat.bin"
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={sec}", LIB, str(tmp_path / "copy.so")],
-                   check=True, capture_output=True)
+def kernel_metadata(tmp_path, lib=None):
+    """{kernel symbol: {field: value}} from the notes of all gfx950 code objects of the library."""
+    with open(lib or LIB, "rb") as f:
+        objects = gfx950_code_objects(f.read())
     meta = {}
-    for i, co in enumerate(gfx950_code_objects(sec.read_bytes())):
+    for i, co in enumerate(objects):
         f = tmp_path / f"co{i}.o"
         f.write_bytes(co)
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(f)], check=True, capture_output=True,
