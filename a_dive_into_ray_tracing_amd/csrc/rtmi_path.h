@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "../../include/rtmi.h"
+#include "rtmi_accept.h"
 
 #ifndef RTMI_STATS
 #define RTMI_STATS 0
@@ -731,23 +732,17 @@ __device__ __forceinline__ void sphere_test(const float4 sp, V3<float> d, float 
 // sphere.h:30-38 root logic, closed interval [0.001, t_max]; the reference's
 // "later object wins ties" (hittable_list.h:25-31) made order-independent: a
 // root equal to t_max replaces the hit only for a larger scene index, so any
-// visiting order gives the in-order loop's hit.  The second root counts only
-// when the first is rejected; both are formed and selected (no branch:
-// measured faster than forming the second only when needed).
+// visiting order gives the in-order loop's hit.  The acceptance itself is
+// rtmi_accept.h's accept_root: both roots are formed (no branch: measured
+// faster than forming the second only when needed), one is selected
+// (r1 <= r2 always) and tested once, and `idx > best` is formed only for an
+// exact tie (7 compares -> 4; 50.0 -> 33.1 cycles a call,
+// profiles/r11/resolve/valu_forms.txt).
 __device__ __forceinline__ void resolve_root(int32_t idx, float hb, float disc, float inv_a, float &t_max,
                                              int32_t &best) {
-  const float sq = dsqrt(disc);
-  const float r1 = (-hb - sq) * inv_a, r2 = (-hb + sq) * inv_a;
-  const bool later = idx > best;
-  // bitwise, not short-circuit: compare masks combined by scalar ops instead
-  // of nested exec-mask branches (config 2: 23.55 -> 23.25 ms,
-  // profiles/r03/ab_accept.txt)
-  const bool ok1 = !(r1 < 0.001f) & ((r1 < t_max) | ((r1 == t_max) & later));
-  const bool ok2 = !(r2 < 0.001f) & ((r2 < t_max) | ((r2 == t_max) & later));
-  if (ok1 || ok2) {
-    t_max = ok1 ? r1 : r2;
-    best = idx;
-  }
+  float r1, r2;
+  root_pair(hb, dsqrt(disc), inv_a, r1, r2);
+  if (accept_root(r1, r2, t_max, [&] { return idx > best; })) best = idx;
 }
 
 // resolve_root for the grid walk, whose hits are named by record-slot keys
@@ -757,27 +752,18 @@ __device__ __forceinline__ void resolve_root(int32_t idx, float hb, float disc, 
 template <bool GMEM = false>
 __device__ __forceinline__ void resolve_key(uint32_t key, float hb, float disc, float inv_a, float &t_max,
                                             int32_t &best_key, uint32_t idx_base, const char *gmem = nullptr) {
-  const float sq = dsqrt(disc);
-  const float r1 = (-hb - sq) * inv_a, r2 = (-hb + sq) * inv_a;
-  const bool g1 = !(r1 < 0.001f), g2 = !(r2 < 0.001f);
-  bool ok1 = g1 & (r1 < t_max), ok2 = g2 & (r2 < t_max);
-  const bool e1 = g1 & (r1 == t_max), e2 = g2 & (r2 == t_max);
-  if (__builtin_expect(e1 | e2, 0)) {
+  float r1, r2;
+  root_pair(hb, dsqrt(disc), inv_a, r1, r2);
+  const bool ok = accept_root(r1, r2, t_max, [&] {
     const uint32_t rec_base = GMEM ? 0u : lds_address(rtmi_bvh_lds);
     const uint32_t bk = best_key < 0 ? key : uint32_t(best_key);
     auto u16 = [&](uint32_t a) {
       if constexpr (GMEM) return uint32_t(*reinterpret_cast<const uint16_t *>(gmem + a));
       else return lds_u16(a);
     };
-    const bool later = (best_key < 0) | (u16(idx_base + ((key - rec_base) >> 3)) >
-                                         u16(idx_base + ((bk - rec_base) >> 3)));
-    ok1 |= e1 & later;
-    ok2 |= e2 & later;
-  }
-  if (ok1 || ok2) {
-    t_max = ok1 ? r1 : r2;
-    best_key = int32_t(key);
-  }
+    return (best_key < 0) | (u16(idx_base + ((key - rec_base) >> 3)) > u16(idx_base + ((bk - rec_base) >> 3)));
+  });
+  if (ok) best_key = int32_t(key);
 }
 
 // The big spheres (the ones kept out of the BVH / grid: the R = 1000 ground
@@ -1031,17 +1017,29 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
         const float texit = __builtin_fminf(tnx, __builtin_fminf(tny, tnz));
         if constexpr (FLAT_Y) {
           // the same step without nested branches: x when its face is nearest
-          // (ties to x), the y face ends the walk, else z (selects: 19.92 vs
-          // 20.06 ms, profiles/r03/ab_dda_select_shade_uniform.txt)
+          // (ties to x), the y face ends the walk, else z (19.92 vs 20.06 ms,
+          // profiles/r03/ab_dda_select_shade_uniform.txt) — and without
+          // selects on the walk's state: the step adds 1 to kx or to kz (one
+          // select forms the 1.0 / 0.0), then BOTH face parameters are
+          // recomputed from their counters.  tn == fma(k, dt, t0) holds for the
+          // axis not stepped, so its recomputation changes nothing: after a
+          // step that is how tn was formed, and at k = 0 fma(0, dt, t0) is t0 up
+          // to the sign of a zero, which no comparison sees (dt = |h * inv| is
+          // finite, safe_inv bounding |inv| by 1e20, so 0 * dt is 0 and not NaN).
+          // The grid's edge is tested after the step: the counters are integers
+          // below 2^16, so k + 1 > kmax is k >= kmax on the stepped axis, and the
+          // other axis' k <= kmax held already.  What a leaving lane steps to is
+          // never read.  (8 selects and 4 compares -> 2 and 6: 56.1 -> 49.8
+          // cycles a step, profiles/r11/resolve/valu_forms.txt.)
           const bool sx = (tnx <= tny) & (tnx <= tnz);
           const bool sy = !sx & (tny <= tnz);
-          const bool leave = !(texit < t_max) | sy | ((sx ? kx : kz) >= (sx ? kmx : kmz));
-          if (leave) break;
-          kx = sx ? kx + 1.0f : kx;
-          kz = sx ? kz : kz + 1.0f;
-          tnx = sx ? __builtin_fmaf(kx, dtx, t0x) : tnx;
-          tnz = sx ? tnz : __builtin_fmaf(kz, dtz, t0z);
+          const float sxf = sx ? 1.0f : 0.0f;
+          kx += sxf;
+          kz += 1.0f - sxf;
+          tnx = __builtin_fmaf(kx, dtx, t0x);
+          tnz = __builtin_fmaf(kz, dtz, t0z);
           cell += sx ? dcx : dcz;
+          if (!(texit < t_max) | sy | (kx > kmx) | (kz > kmz)) break;
           continue;
         }
         if (!(texit < t_max)) break;  // the closest hit so far lies in the cells walked
