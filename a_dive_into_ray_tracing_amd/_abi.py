@@ -56,6 +56,13 @@ class RtNwAdaptStats(C.Structure):
                 ("active", C.POINTER(C.c_int64)), ("cap", C.c_int32), ("pad", C.c_int32)]
 
 
+class RtNwDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+NW_DENOISE_DEMODULATE, NW_DENOISE_NO_EDGES = 1, 2
+
 NW_ADAPT_ON_PASS = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64)  # rt_nw_adapt_on_pass
 
 
@@ -234,6 +241,21 @@ SIGNATURES = {
     "rt_nw_adapt_save": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 4 + [C.c_uint64]),
     "rt_nw_adapt_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 6 + [C.c_uint64]),
     "rt_nw_adapt_info": (C.c_int, [C.c_char_p, _ip, C.POINTER(C.c_uint64)]),
+    # denoising of the Next-Week renderer
+    "rt_nw_render_features": (C.c_int, [C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 3 + [C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
+    "rt_nw_adapt_variance": (C.c_int, [_lp, C.POINTER(C.c_uint64), _ip, C.c_int32, C.c_int32, _fp]),
+    "rt_nw_denoise_params_default": (C.c_int, [C.POINTER(RtNwDenoiseParams)]),
+    "rt_nw_denoise_params_check": (C.c_int, [C.POINTER(RtNwDenoiseParams)]),
+    "rt_nw_denoise": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtNwDenoiseParams),
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_nw_denoise_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _fp, _fp, _fp, C.POINTER(RtNwDenoiseParams), _fp, _fp]),
+    "rt_nw_render_denoised": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(RtNwCamera)] + [C.c_int32] * 5 + [C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                                             C.c_uint64, C.c_char_p, C.c_double, _fp, _ip, _dp,
+                                                                             C.POINTER(RtNwAdaptStats), NW_ADAPT_ON_PASS,
+                                                                             C.c_void_p, C.c_int32, C.POINTER(RtNwDenoiseParams), _fp],
+    ),
 }
 
 _lib = None

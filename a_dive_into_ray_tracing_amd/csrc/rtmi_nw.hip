@@ -711,6 +711,78 @@ template <int WALK> __global__ __launch_bounds__(256) void debug_records_kernel(
   p[6] = rc.u; p[7] = rc.v;
 }
 
+// fixed()'s signed twin (the feature normals): NaN -> 0, clamped to [-64, 64], truncated toward zero
+__device__ __forceinline__ int64_t fixed_signed(float c) {
+  const float g = c == c ? __builtin_amdgcn_fmed3f(c, -64.0f, 64.0f) : 0.0f;
+  const float m = __builtin_fabsf(g);
+  const uint32_t hi = uint32_t(m);
+  const uint32_t lo = uint32_t((m - float(hi)) * 4294967296.0f);
+  const int64_t v = int64_t((uint64_t(hi) << 32) | lo);
+  return g < 0.0f ? -v : v;
+}
+// ... and the one of a ray parameter: NaN -> 0, clamped to [0, 2^20]
+__device__ __forceinline__ int64_t fixed_t(float c) {
+  const float g = c == c ? __builtin_amdgcn_fmed3f(c, 0.0f, 1048576.0f) : 0.0f;
+  const uint32_t hi = uint32_t(g);
+  const uint32_t lo = uint32_t((g - float(hi)) * 4294967296.0f);
+  return int64_t((uint64_t(hi) << 32) | lo);
+}
+
+// First-hit feature buffers (rt_nw_render_features, the denoiser's guides): one thread per pixel, which loops over
+// the camera samples s < fspp.  Sample (i, j, s) is segment 0 of trace_kernel's (i, j, s), draw for draw; the sums
+// are int64 fixed point per thread, so the means do not depend on anything but the samples.
+struct FeatArgs {
+  int32_t fspp, has_attr;
+  float *out;  // {a.rgb, n.xyz, z, cov} per pixel
+};
+template <int WALK> __global__ __launch_bounds__(256) void features_kernel(View sc, Args a, FeatArgs f) {
+  stage_scene<false, false, WALK == kWalkGrid>(sc);  // (grid: ends with the block barrier, before any thread leaves)
+  const uint32_t px = blockIdx.x * blockDim.x + threadIdx.x;
+  if (px >= uint32_t(a.W) * uint32_t(a.H)) return;
+  const int j = int(px / uint32_t(a.W)), i = int(px - uint32_t(j) * uint32_t(a.W));
+  int64_t sa[3] = {0, 0, 0}, sn[3] = {0, 0, 0}, st = 0;
+  int32_t hits = 0;
+  NwCount cnt{0, 0, 0, 0};
+  for (int s = 0; s < f.fspp; ++s) {
+    Xoro rng;
+    rng.init(a.seed, uint64_t(j) * uint64_t(a.W) + uint64_t(i), uint32_t(s));
+    float ju, jv;
+    rng.pair(ju, jv);
+    V o, d;
+    get_ray<true, float>(a.cam, (float(i) + ju) / float(a.W), (float(j) + jv) / float(a.H), rng, o, d);
+    const float time = __builtin_fmaf(rng.uni(), a.time1 - a.time0, a.time0);
+    const uint64_t seg_key = sc.has_media ? rng.next() : 0ull;
+    float t;
+    int face;
+    int32_t sub = -1;
+    const int32_t k = walk_closest<WALK, 2>(sc, o, d, time, seg_key, t, face, sub, &cnt);
+    V alb = mk(sc.bg[0], sc.bg[1], sc.bg[2]);
+    if (k >= 0) {
+      const Rec rc = walk_rec<WALK>(sc, k, sub, o, d, time, t, face, f.has_attr);
+      const Mat m = sc.mat[rc.mat];
+      alb = m.kind == kDielectric ? mk(1.0f, 1.0f, 1.0f) : tex_value<false>(sc, m.tex, rc.u, rc.v, rc.p);
+      if (k < sc.nobj) {  // (a medium has no surface)
+        sn[0] += fixed_signed(rc.n.x);
+        sn[1] += fixed_signed(rc.n.y);
+        sn[2] += fixed_signed(rc.n.z);
+      }
+      st += fixed_t(t);
+      ++hits;
+    }
+    sa[0] += fixed(alb.x);
+    sa[1] += fixed(alb.y);
+    sa[2] += fixed(alb.z);
+  }
+  float *out = f.out + 8 * size_t(px);
+  const double n = double(f.fspp);
+  for (int c = 0; c < 3; ++c) {
+    out[c] = float(double(sa[c]) * 0x1p-32 / n);
+    out[3 + c] = float(double(sn[c]) * 0x1p-32 / n);
+  }
+  out[6] = hits > 0 ? float(double(st) * 0x1p-32 / double(hits)) : 0.0f;
+  out[7] = float(double(hits) / n);
+}
+
 }  // namespace nw
 }  // namespace rtmi
 
@@ -820,6 +892,7 @@ struct rt_nw_ctx {
     bool used = false;
   } adapt_list[2];
   int adapt_slot = 0;
+  DenoiseScratch denoise;  // the filter's images (rt_nw_denoise, rtmi_nw_denoise.hip)
   unsigned long long *segments = nullptr;
   unsigned *counter = nullptr;  // persistent kernel's work-item counter
   int32_t persist_blocks = 0;   // resident 16-wave blocks (CUs x blocks per CU), BVH kernels
@@ -858,7 +931,7 @@ struct rt_nw_ctx {
                     (void *)pperm, (void *)img, (void *)imgd, (void *)nodes, (void *)accum, (void *)scratch, (void *)segments,
                     (void *)counter, (void *)grid_cells, (void *)grid_refs, (void *)grid_big, (void *)pass_accum, (void *)adapt_sum,
                     (void *)adapt_m2, (void *)adapt_n, (void *)adapt_list[0].tiles, (void *)adapt_list[0].masks,
-                    (void *)adapt_list[1].tiles, (void *)adapt_list[1].masks})
+                    (void *)adapt_list[1].tiles, (void *)adapt_list[1].masks, denoise.p})
       if (p) (void)hipFree(p);
     for (auto &l : adapt_list)
       if (l.done) (void)hipEventDestroy(l.done);
@@ -2112,6 +2185,106 @@ RTMI_EXPORT int rt_nw_debug_hits(rt_nw_ctx *ctx, const float *rays, const uint64
 RTMI_EXPORT int rt_nw_debug_records(rt_nw_ctx *ctx, const float *rays, const uint64_t *keys, int32_t n, int32_t *out_id,
                                     float *out_t, float *out_pnuv, int32_t *out_mat) {
   return debug_rays(ctx, "rt_nw_debug_records", true, rays, keys, n, out_id, out_t, out_mat, out_pnuv);
+}
+
+// ---------------------------------------------------------------------------
+// denoising (DESIGN.md §9 "Denoising"): the feature buffers and the driver; the filter is rtmi_nw_denoise.hip
+// ---------------------------------------------------------------------------
+namespace {
+const void *const kFeaturesKernels[kWalks] = {(const void *)features_kernel<kWalkBvh>, (const void *)features_kernel<kWalkGrid>,
+                                              (const void *)features_kernel<kWalkInst>, (const void *)features_kernel<kWalkMove>,
+                                              (const void *)features_kernel<kWalkAffine>};
+}  // namespace
+
+RTMI_EXPORT int rt_nw_render_features(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t fspp, uint64_t seed,
+                                      float *dev_feat, float *host_feat, void *stream) {
+  const char *who = "rt_nw_render_features";
+  if (int rc = check_rows_args(ctx, cam, W, H, 1, 1, 0, 1, std::max(H, 1), 0, false, who)) return rc;
+  if (!dev_feat && !host_feat) return set_error(RT_EINVAL, "%s: no output", who);
+  if (fspp < 1 || fspp > 1024) return set_error(RT_EINVAL, "%s: fspp %d outside 1..1024", who, fspp);
+  if (int64_t(W) * H >= (int64_t(1) << 31)) return set_error(RT_EINVAL, "%s: more than 2^31 pixels", who);
+  Guard g(ctx->device);
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const bool grid = accel_used(ctx) == RT_NW_ACCEL_GRID;
+  const size_t lds = grid ? grid_bytes(ctx) : 0, npix = size_t(W) * size_t(H), n = npix * 8;
+  if (lds > kCuLds) return set_error(RT_EUNSUPPORTED, "%s: grid of %zu B exceeds a CU's LDS", who, lds);
+  float *out = dev_feat;
+  if (!out) {  // through the context's float scratch, which renders share
+    if (n > ctx->scratch_cap) {
+      if (int rc = adapt_wait(ctx)) return rc;
+      ctx->scratch_cap = 0;
+      if (int rc = alloc_copy<float>(&ctx->scratch, nullptr, n)) return rc;
+      ctx->scratch_cap = n;
+    }
+    out = ctx->scratch;
+  }
+  if (int rc = take_turn(ctx, st)) return rc;
+  View v = view_of(ctx);
+  Args a = camera_args(cam, W, H, 1, seed);
+  FeatArgs f{fspp, ctx->nattr > 0 ? 1 : 0, out};
+  void *args[] = {&v, &a, &f};
+  hipError_t e = hipLaunchKernel(kFeaturesKernels[walk_of(ctx, grid)], dim3(unsigned((npix + 255) / 256)), dim3(256), args, lds, st);
+  if (e == hipSuccess && host_feat) e = hipMemcpyAsync(host_feat, out, n * sizeof(float), hipMemcpyDeviceToHost, st);
+  (void)hipEventRecord(ctx->last_done, st);
+  if (e == hipSuccess && host_feat) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return set_error(RT_EHIP, "%s: %s", who, hipGetErrorString(e));
+  return RT_OK;
+}
+
+// the denoiser's side of the context (rtmi_nw_internal.h)
+namespace rtmi {
+namespace nw {
+int ctx_link(rt_nw_ctx *ctx, CtxLink &out) {
+  if (!ctx) return set_error(RT_EINVAL, "null ctx");
+  out.device = ctx->device;
+  out.stream = ctx->stream;
+  out.scratch = &ctx->denoise;
+  return RT_OK;
+}
+int ctx_begin(rt_nw_ctx *ctx, void *stream) { return take_turn(ctx, static_cast<hipStream_t>(stream)); }
+void ctx_end(rt_nw_ctx *ctx, void *stream) { (void)hipEventRecord(ctx->last_done, static_cast<hipStream_t>(stream)); }
+int ctx_idle(rt_nw_ctx *ctx) { return adapt_wait(ctx); }
+}  // namespace nw
+}  // namespace rtmi
+
+RTMI_EXPORT int rt_nw_render_denoised(rt_nw_ctx *ctx, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
+                                      int32_t min_spp, int32_t max_spp, int32_t pass_spp, double threshold, double floor,
+                                      int32_t dilate, int32_t max_depth, uint64_t seed, const char *checkpoint, double time_limit,
+                                      float *mean_out, int32_t *n_out, double *err_out, rt_nw_adapt_stats *stats,
+                                      rt_nw_adapt_on_pass on_pass, void *user, int32_t fspp, const rt_nw_denoise_params *p,
+                                      float *denoised_out) {
+  const char *who = "rt_nw_render_denoised";
+  if (!denoised_out) return set_error(RT_EINVAL, "%s: null denoised_out", who);
+  if (fspp < 1 || fspp > 1024) return set_error(RT_EINVAL, "%s: fspp %d outside 1..1024", who, fspp);
+  if (p)
+    if (int rc = rt_nw_denoise_params_check(p)) return rc;
+  if (int rc = rt_nw_render_adaptive(ctx, scene, cam, W, H, min_spp, max_spp, pass_spp, threshold, floor, dilate, max_depth, seed,
+                                     checkpoint, time_limit, mean_out, n_out, err_out, stats, on_pass, user))
+    return rc;
+  if (int64_t(W) * H >= (int64_t(1) << 31)) return set_error(RT_EINVAL, "%s: more than 2^31 pixels", who);
+  Guard g(ctx->device);
+  const size_t npix = size_t(W) * size_t(H);
+  std::vector<int64_t> sum(npix * 3);
+  std::vector<uint64_t> m2(npix);
+  std::vector<int32_t> n(npix);
+  std::vector<float> var(npix);
+  if (int rc = rt_nw_adapt_export(ctx, sum.data(), m2.data(), n.data(), npix)) return rc;
+  if (int rc = rt_nw_adapt_variance(sum.data(), m2.data(), n.data(), W, H, var.data())) return rc;
+  // one device allocation: mean (in place the filtered image) | var | feat
+  DevBuf<float> d;
+  HIP_TRY(d.alloc(npix * 12));
+  float *d_mean = d.p, *d_var = d.p + 3 * npix, *d_feat = d.p + 4 * npix;
+  HIP_TRY(hipMemcpyAsync(d_var, var.data(), npix * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  int rc = rt_nw_adapt_resolve(ctx, d_mean, nullptr, nullptr);
+  if (rc == RT_OK) rc = rt_nw_render_features(ctx, cam, W, H, fspp, seed, d_feat, nullptr, nullptr);
+  if (rc == RT_OK) rc = rt_nw_denoise(ctx, W, H, d_mean, d_var, d_feat, p, d_mean, nullptr, nullptr);
+  hipError_t e = hipSuccess;
+  if (rc == RT_OK) e = hipMemcpyAsync(denoised_out, d_mean, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (before the allocation and var go)
+  if (rc != RT_OK) return rc;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return set_error(RT_EHIP, "%s: %s", who, hipGetErrorString(e));
+  return RT_OK;
 }
 
 // Analysis builds only (RTMI_NW_PHASES): the phase cycle sums since the last

@@ -11,6 +11,16 @@
 //                  [--obj-texture FILE.ppm] [--obj-copies N] [--obj-move DX,DY,DZ] [--obj-tumble] [--width W] ...
 //   either form: [--shutter T0,T1] [--pass-spp N] [--checkpoint FILE] [--time-limit SECONDS] [--pfm FILE]
 //                [--adaptive THRESHOLD [--min-spp N] [--spp-map FILE.pfm]]
+//                [--denoise [--denoise-iters N] [--features-spp N]] [--aov PREFIX]
+//
+// --denoise writes the filtered image (rt_nw_render_denoised: first-hit features
+// of --features-spp samples per pixel, default 16, the variance of the adaptive
+// accumulator and --denoise-iters a-trous levels, default 5) to --out / --pfm.
+// The variance needs the second moments, so without --adaptive the render goes
+// through the adaptive accumulator with every pixel active (threshold 0: the
+// plain render of --spp samples, in passes of --pass-spp, default kDefaultPassSpp).
+// --aov PREFIX writes PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm (the
+// depth in all three channels) and, with --denoise, PREFIX_noisy.pfm.
 //
 // --adaptive THRESHOLD samples every pixel until the relative standard error of
 // its mean (rt_nw_adapt_criterion, floor 0.03, dilation 1) is at most THRESHOLD
@@ -115,7 +125,9 @@ int main(int argc, char **argv) {
   std::string scene = "8", out = "-", texture, obj, obj_mat = "lambertian", obj_texture, checkpoint, pfm, spp_map;
   int pass_spp = 0, min_spp = 16;
   double time_limit = -1, adaptive = -1;
-  bool min_given = false;
+  bool min_given = false, denoise = false;
+  int denoise_iters = 5, features_spp = 16;
+  std::string aov;
   bool scene_given = false, obj_smooth = false, obj_gen = false;
   int W = 800, H = -1, spp = 5000, depth = 50, p6 = 0, rtl = 0, obj_copies = 1;
   bool copies_given = false, move_given = false, shutter_given = false, tumble = false;
@@ -168,6 +180,10 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[a], "--pfm")) pfm = need("--pfm");
     else if (!std::strcmp(argv[a], "--spp-map")) spp_map = need("--spp-map");
     else if (!std::strcmp(argv[a], "--min-spp")) { min_spp = std::atoi(need("--min-spp")); min_given = true; }
+    else if (!std::strcmp(argv[a], "--denoise")) denoise = true;
+    else if (!std::strcmp(argv[a], "--denoise-iters")) denoise_iters = std::atoi(need("--denoise-iters"));
+    else if (!std::strcmp(argv[a], "--features-spp")) features_spp = std::atoi(need("--features-spp"));
+    else if (!std::strcmp(argv[a], "--aov")) aov = need("--aov");
     else if (!std::strcmp(argv[a], "--adaptive")) {
       if (!numbers(need("--adaptive"), &adaptive, 1) || adaptive < 0) { std::fprintf(stderr, "--adaptive takes THRESHOLD >= 0\n"); return 2; }
     }
@@ -193,6 +209,12 @@ int main(int argc, char **argv) {
                            "         error of its mean is at most THRESHOLD, between --min-spp (default 16) and --spp samples, in\n"
                            "         passes of --pass-spp (default %d) over the pixels still active; --checkpoint, --time-limit,\n"
                            "         --out and --pfm as above; --spp-map: the per-pixel sample counts as a PFM\n"
+                           "  --denoise [--denoise-iters N] [--features-spp N]: write the image filtered by the edge-avoiding a-trous\n"
+                           "         wavelet (N levels, 1..8, default 5) guided by first-hit features of N samples per pixel (1..1024,\n"
+                           "         default 16) and the per-pixel variance.  The variance needs the adaptive accumulator's second\n"
+                           "         moments: without --adaptive the render goes through that accumulator with every pixel active\n"
+                           "         (the plain render of --spp samples, --spp >= 2, in passes of --pass-spp, default %d)\n"
+                           "  --aov PREFIX: PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm and, with --denoise, PREFIX_noisy.pfm\n"
                            "  --obj: the mesh scaled and centred into the box [-1,1] x [0,2] x [-1,1] on a checker\n"
                            "         ground, one 3 x 3 light (emission 6) at y = 5, background (0.05, 0.07, 0.12);\n"
                            "         camera from (3.2, 2.4, 4.8) at (0, 1, 0), vfov 30, no aperture; not with --scene\n"
@@ -204,7 +226,7 @@ int main(int argc, char **argv) {
                            "         times [0, 1] (motion blur under the default shutter)\n"
                            "  --obj-tumble (needs --obj): every copy as an affine placement of the shared mesh, scaled by\n"
                            "         0.75 + 0.25 sin(2.9 q), turned 37 q degrees about a skew axis and stood on the ground\n",
-                   argv[0], argv[0], kDefaultPassSpp, kDefaultAdaptPassSpp);
+                   argv[0], argv[0], kDefaultPassSpp, kDefaultAdaptPassSpp, kDefaultPassSpp);
       return 2;
     }
   }
@@ -237,6 +259,18 @@ int main(int argc, char **argv) {
   if (H < 0) H = W;  // aspect_ratio = 1.0, main.cu:517-519
   if (pass_spp < 0) { std::fprintf(stderr, "--pass-spp takes a count >= 1\n"); return 2; }
   if (adaptive < 0 && (min_given || !spp_map.empty())) { std::fprintf(stderr, "--min-spp and --spp-map need --adaptive\n"); return 2; }
+  if (denoise && (denoise_iters < 1 || denoise_iters > 8 || features_spp < 1 || features_spp > 1024)) {
+    std::fprintf(stderr, "--denoise-iters takes 1..8 and --features-spp 1..1024\n");
+    return 2;
+  }
+  if (!aov.empty() && (features_spp < 1 || features_spp > 1024)) { std::fprintf(stderr, "--features-spp takes 1..1024\n"); return 2; }
+  const bool all_active = denoise && adaptive < 0;  // the plain render through the adaptive accumulator
+  if (all_active) {
+    if (spp < 2) { std::fprintf(stderr, "--denoise needs --spp >= 2\n"); return 2; }
+    if (pass_spp == 0) pass_spp = kDefaultPassSpp;
+    adaptive = 0;
+    min_spp = spp;
+  }
   if (adaptive >= 0 && pass_spp == 0) pass_spp = kDefaultAdaptPassSpp;
   if (adaptive >= 0 && (min_spp < 0 || min_spp > spp || spp < 2)) { std::fprintf(stderr, "--adaptive needs 0 <= --min-spp <= --spp and --spp >= 2\n"); return 2; }
   if (pass_spp == 0 && (!checkpoint.empty() || time_limit >= 0)) pass_spp = kDefaultPassSpp;
@@ -298,12 +332,24 @@ int main(int argc, char **argv) {
   int div = 0;              // what the sums are divided by for the image: spp, or 1 where sum holds means (--adaptive)
   double rendered = -1;     // samples this run rendered
   std::vector<int32_t> counts;
+  std::vector<float> filtered;  // --denoise: the filtered means (sum then holds the noisy ones)
   if (adaptive >= 0) {
     counts.resize(size_t(W) * H);
     rt_nw_adapt_stats st{};
-    if ((rc = rt_nw_render_adaptive(ctx, s, &cam, W, H, min_spp, spp, pass_spp, adaptive, 0.03, 1, depth, seed,
-                                    checkpoint.empty() ? nullptr : checkpoint.c_str(), time_limit, sum.data(), counts.data(), nullptr, &st, nullptr, nullptr)))
+    if (denoise) {
+      rt_nw_denoise_params dp;
+      if ((rc = rt_nw_denoise_params_default(&dp))) return die("rt_nw_denoise_params_default", rc);
+      dp.iterations = denoise_iters;
+      filtered.resize(sum.size());
+      if ((rc = rt_nw_render_denoised(ctx, s, &cam, W, H, min_spp, spp, pass_spp, adaptive, 0.03, 1, depth, seed,
+                                      checkpoint.empty() ? nullptr : checkpoint.c_str(), time_limit, sum.data(), counts.data(), nullptr,
+                                      &st, nullptr, nullptr, features_spp, &dp, filtered.data())))
+        return die("rt_nw_render_denoised", rc);
+    } else if ((rc = rt_nw_render_adaptive(ctx, s, &cam, W, H, min_spp, spp, pass_spp, adaptive, 0.03, 1, depth, seed,
+                                           checkpoint.empty() ? nullptr : checkpoint.c_str(), time_limit, sum.data(), counts.data(),
+                                           nullptr, &st, nullptr, nullptr))) {
       return die("rt_nw_render_adaptive", rc);
+    }
     std::fprintf(stderr, "{\"adaptive\": %g, \"passes\": %d, \"stopped_by_time_limit\": %d, \"total_samples\": %lld, "
                          "\"mean_spp\": %.3f, \"share_at_max\": %.4f}\n",
                  adaptive, st.passes, st.stopped, (long long)st.total_samples, double(st.total_samples) / (double(W) * H),
@@ -349,6 +395,18 @@ int main(int argc, char **argv) {
                "{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"seconds\": %.6f, "
                "\"msamples_per_s\": %.3f, \"segments_per_sample\": %.4f}\n",
                which, W, H, spp, depth, seconds, rendered / seconds / 1e6, rendered > 0 ? double(segs) / rendered : 0.0);
+  if (!aov.empty()) {
+    std::vector<float> feat(size_t(W) * H * 8), plane(size_t(W) * H * 3);
+    if ((rc = rt_nw_render_features(ctx, &cam, W, H, features_spp, seed, nullptr, feat.data(), nullptr))) return die("rt_nw_render_features", rc);
+    static const char *const kinds[3] = {"_albedo.pfm", "_normal.pfm", "_depth.pfm"};
+    for (int k = 0; k < 3; ++k) {
+      for (size_t p = 0; p < size_t(W) * H; ++p)
+        for (int c = 0; c < 3; ++c) plane[3 * p + c] = feat[8 * p + (k < 2 ? 3 * k + c : 6)];
+      if ((rc = rt_write_pfm((aov + kinds[k]).c_str(), plane.data(), W, H, 1))) return die("rt_write_pfm", rc);
+    }
+    if (denoise && (rc = rt_write_pfm((aov + "_noisy.pfm").c_str(), sum.data(), W, H, div ? div : spp))) return die("rt_write_pfm", rc);
+  }
+  if (denoise) sum.swap(filtered);  // (--out and --pfm carry the filtered image)
   rt_nw_ctx_destroy(ctx);
   rt_nw_scene_destroy(s);
 

@@ -110,5 +110,24 @@ int adapt_ckpt_read(const char *path, CkptHeader &h, std::vector<int64_t> *sum, 
 // FNV-1a 64 of the camera's bytes (the shutter included)
 uint64_t camera_hash(const rt_nw_camera *cam);
 
+// What the denoiser (rtmi_nw_denoise.hip) uses of a context, whose layout stays with rtmi_nw.hip: the device, the
+// context's stream (a hipStream_t) and the filter's scratch images, one device allocation that the context's
+// destructor frees.  ctx_begin / ctx_end put work on `stream` into the context's order as every launch of
+// rtmi_nw.hip is (it waits for the last work on another stream, and records its own end); ctx_idle waits for
+// everything the context has launched, before the scratch is replaced.
+struct DenoiseScratch {
+  void *p = nullptr;
+  size_t pixels = 0;
+};
+struct CtxLink {
+  int32_t device = 0;
+  void *stream = nullptr;
+  DenoiseScratch *scratch = nullptr;
+};
+int ctx_link(rt_nw_ctx *ctx, CtxLink &out);
+int ctx_begin(rt_nw_ctx *ctx, void *stream);
+void ctx_end(rt_nw_ctx *ctx, void *stream);
+int ctx_idle(rt_nw_ctx *ctx);
+
 }  // namespace nw
 }  // namespace rtmi

@@ -2284,6 +2284,45 @@ RTMI_EXPORT int rt_nw_adapt_criterion(const int64_t *sum, const uint64_t *m2, co
   return RT_OK;
 }
 
+// The variance of each pixel's mean channel sum (the denoiser's guide), from the criterion's moments in its float64
+// order: var = max(0, ex2 - mean^2) / (n - 1), which is the criterion's var / n.  Fewer than two samples: +inf.
+RTMI_EXPORT int rt_nw_adapt_variance(const int64_t *sum, const uint64_t *m2, const int32_t *n, int32_t W, int32_t nrows, float *var) {
+  if (!sum || !m2 || !n || !var) return set_error(RT_EINVAL, "rt_nw_adapt_variance: null argument");
+  if (W < 1 || nrows < 1 || int64_t(W) * nrows >= (int64_t(1) << 40)) return set_error(RT_EINVAL, "rt_nw_adapt_variance: bad size");
+  const size_t npix = size_t(W) * size_t(nrows);
+  for (size_t p = 0; p < npix; ++p)
+    if (n[p] < 0) return set_error(RT_EINVAL, "rt_nw_adapt_variance: negative sample count");
+  for (size_t p = 0; p < npix; ++p) {
+    const int32_t k = n[p];
+    double v = std::numeric_limits<double>::infinity();
+    if (k >= 2) {
+      const double nn = double(k);
+      const double mean = double(sum[3 * p] + sum[3 * p + 1] + sum[3 * p + 2]) * 0x1p-32 / nn;
+      const double ex2 = double(m2[p]) * 0x1p-28 / nn;
+      v = std::max(0.0, ex2 - mean * mean) / (nn - 1.0);
+    }
+    var[p] = float(v);
+  }
+  return RT_OK;
+}
+
+// The denoiser's parameters (rt_nw_denoise; the filter itself is rtmi_nw_denoise.hip): host only
+RTMI_EXPORT int rt_nw_denoise_params_default(rt_nw_denoise_params *p) {
+  if (!p) return set_error(RT_EINVAL, "rt_nw_denoise_params_default: null argument");
+  *p = rt_nw_denoise_params{5, 4.0f, 128.0f, 1.0f, RT_NW_DENOISE_DEMODULATE};
+  return RT_OK;
+}
+
+RTMI_EXPORT int rt_nw_denoise_params_check(const rt_nw_denoise_params *p) {
+  if (!p) return set_error(RT_EINVAL, "rt_nw_denoise_params_check: null argument");
+  if (p->iterations < 1 || p->iterations > 8) return set_error(RT_EINVAL, "rt_nw_denoise: iterations %d outside 1..8", p->iterations);
+  for (float s : {p->sigma_l, p->sigma_n, p->sigma_z})
+    if (!std::isfinite(s) || !(s > 0.0f)) return set_error(RT_EINVAL, "rt_nw_denoise: every sigma must be finite and > 0");
+  if (p->flags & ~uint32_t(RT_NW_DENOISE_DEMODULATE | RT_NW_DENOISE_NO_EDGES))
+    return set_error(RT_EINVAL, "rt_nw_denoise: unknown flag bits 0x%x", p->flags);
+  return RT_OK;
+}
+
 RTMI_EXPORT int rt_nw_accum_info(const char *path, int32_t out8[8], uint64_t out3[3]) {
   if (!path || !out8 || !out3) return set_error(RT_EINVAL, "rt_nw_accum_info: null argument");
   CkptHeader h{};

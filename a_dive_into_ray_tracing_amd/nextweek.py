@@ -18,10 +18,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import NW_ADAPT_ON_PASS, RtNwAdaptStats, RtNwCamera, RtNwFlat, check, load
+from ._abi import (NW_ADAPT_ON_PASS, NW_DENOISE_DEMODULATE, NW_DENOISE_NO_EDGES, RtNwAdaptStats, RtNwCamera, RtNwDenoiseParams,
+                   RtNwFlat, check, load)
 
 __all__ = ["Scene", "NwRenderer", "camera", "preset", "obj_stage", "xorwow_uniforms", "load_image", "accum_info", "SCENES",
-           "adapt_criterion", "adapt_info", "ADAPT_FLOOR"]
+           "adapt_criterion", "adapt_info", "ADAPT_FLOOR", "adapt_variance", "denoise_params"]
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -439,6 +440,41 @@ def adapt_criterion(s, m2, n, min_spp, max_spp, threshold, floor=ADAPT_FLOOR, di
     return active, err, count.value
 
 
+def adapt_variance(s, m2, n):
+    """The variance of each pixel's mean channel sum (host only, rt_nw_adapt_variance),
+    the denoiser's guide: from sum [nrows, W, 3], m2 and n [nrows, W] to float32
+    [nrows, W]; +inf where n < 2."""
+    n = np.ascontiguousarray(n, np.int32)
+    if n.ndim != 2:
+        raise ValueError("adapt_variance: n must be [nrows, W]")
+    s, m2 = np.ascontiguousarray(s, np.int64), np.ascontiguousarray(m2, np.uint64)
+    if s.shape != n.shape + (3,) or m2.shape != n.shape:
+        raise ValueError("adapt_variance: sum [nrows, W, 3], m2 and n [nrows, W]")
+    var = np.zeros(n.shape, np.float32)
+    check(load().rt_nw_adapt_variance(s.ctypes.data_as(C.POINTER(C.c_int64)), m2.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      n.ctypes.data_as(_ip), n.shape[1], n.shape[0], var.ctypes.data_as(_fp)),
+          "rt_nw_adapt_variance")
+    return var
+
+
+def denoise_params(iterations=None, sigma_l=None, sigma_n=None, sigma_z=None, demodulate=None, no_edges=False, validate=True):
+    """rt_nw_denoise_params: the library's defaults (5 iterations, sigma_l 4,
+    sigma_n 128, sigma_z 1, demodulation on) with the given fields replaced,
+    checked by rt_nw_denoise_params_check (host only)."""
+    p = RtNwDenoiseParams()
+    check(load().rt_nw_denoise_params_default(C.byref(p)), "rt_nw_denoise_params_default")
+    for name, v in (("iterations", iterations), ("sigma_l", sigma_l), ("sigma_n", sigma_n), ("sigma_z", sigma_z)):
+        if v is not None:
+            setattr(p, name, v)
+    if demodulate is not None:
+        p.flags = (p.flags & ~NW_DENOISE_DEMODULATE) | (NW_DENOISE_DEMODULATE if demodulate else 0)
+    if no_edges:
+        p.flags |= NW_DENOISE_NO_EDGES
+    if validate:
+        check(load().rt_nw_denoise_params_check(C.byref(p)), "rt_nw_denoise_params_check")
+    return p
+
+
 def load_image(path):
     """Decode an image file (the earth texture) to h x w x 3 uint8, row 0 at the top (PIL)."""
     from PIL import Image
@@ -610,8 +646,44 @@ class NwRenderer:
                                       max_depth, seed), "rt_nw_adapt_load")
         self._adapt_shape = (nrows, W)
 
+    # ---- denoising (rt_nw_render_features / rt_nw_denoise) ----------------
+    def features(self, cam, W, H, fspp=16, seed=1984):
+        """First-hit feature buffers [H, W, 8] float32, row 0 at the bottom: mean
+        albedo rgb, mean normal xyz (not unit), mean t of the hits and coverage
+        over fspp camera samples per pixel (rt_nw_render_features)."""
+        out = np.zeros((H, W, 8), np.float32)
+        check(load().rt_nw_render_features(self._h, C.byref(cam), W, H, fspp, seed, None, out.ctypes.data_as(_fp), None),
+              "rt_nw_render_features")
+        return out
+
+    def denoise(self, mean, var, feat, var_out=False, **params):
+        """The edge-avoiding a-trous filter (rt_nw_denoise_host) of mean [H, W, 3]
+        guided by feat [H, W, 8] and var [H, W] (the variance of the mean channel
+        sum, adapt_variance; None: no luminance term).  params: denoise_params'
+        keywords.  Returns the filtered image, and with var_out=True (needs var)
+        also the filtered variance."""
+        mean = np.ascontiguousarray(mean, np.float32)
+        feat = np.ascontiguousarray(feat, np.float32)
+        if mean.ndim != 3 or mean.shape[2] != 3 or feat.shape != mean.shape[:2] + (8,):
+            raise ValueError("denoise: mean [H, W, 3] and feat [H, W, 8]")
+        H, W = mean.shape[:2]
+        v = None
+        if var is not None:
+            v = np.ascontiguousarray(var, np.float32)
+            if v.shape != (H, W):
+                raise ValueError("denoise: var must be [H, W]")
+        if var_out and v is None:
+            raise ValueError("denoise: var_out needs var")
+        p = denoise_params(validate=False, **params)
+        out = np.zeros((H, W, 3), np.float32)
+        vo = np.zeros((H, W), np.float32) if var_out else None
+        check(load().rt_nw_denoise_host(self._h, W, H, mean.ctypes.data_as(_fp), None if v is None else v.ctypes.data_as(_fp),
+                                        feat.ctypes.data_as(_fp), C.byref(p), out.ctypes.data_as(_fp),
+                                        None if vo is None else vo.ctypes.data_as(_fp)), "rt_nw_denoise_host")
+        return (out, vo) if var_out else out
+
     def adaptive(self, cam, W, H, min_spp, max_spp, pass_spp, threshold, floor=ADAPT_FLOOR, dilate=1, max_depth=50, seed=1984,
-                 checkpoint=None, time_limit=None, on_pass=None, stats=None):
+                 checkpoint=None, time_limit=None, on_pass=None, stats=None, denoise=False, fspp=16, denoise_args=None):
         """Sample until no pixel's relative error (adapt_criterion) exceeds
         `threshold`, no pixel above max_spp samples, in passes of pass_spp over
         the active pixels (rt_nw_render_adaptive); resumes from `checkpoint` when
@@ -621,7 +693,9 @@ class NwRenderer:
         that long (one always runs).  Returns (mean [H, W, 3] float32, n [H, W]
         int32, err [H, W] float64); stats (a dict, when given) receives passes,
         stopped, total_samples, pixels_at_max, samples and segments (this call's)
-        and active (pixels per pass)."""
+        and active (pixels per pass).  denoise=True (rt_nw_render_denoised): a
+        fourth value, the image filtered with features of fspp samples per pixel
+        and denoise_args (denoise_params' keywords); the first three are unchanged."""
         mean, n, err = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.int32), np.zeros((H, W), np.float64)
         # (pixels join at different passes, so there can be more than max_spp / pass_spp of them; the log keeps
         # the first 4 max_spp / pass_spp + 64)
@@ -638,19 +712,24 @@ class NwRenderer:
             return 0
 
         cb = NW_ADAPT_ON_PASS(step) if on_pass is not None else NW_ADAPT_ON_PASS()
-        check(load().rt_nw_render_adaptive(self._h, self._scene._h, C.byref(cam), W, H, min_spp, max_spp, pass_spp,
-                                           float(threshold), float(floor), dilate, max_depth, seed,
-                                           None if checkpoint is None else str(checkpoint).encode(),
-                                           -1.0 if time_limit is None else float(time_limit), mean.ctypes.data_as(_fp),
-                                           n.ctypes.data_as(_ip), err.ctypes.data_as(_dp), C.byref(st), cb, None),
-              "rt_nw_render_adaptive")
+        args = (self._h, self._scene._h, C.byref(cam), W, H, min_spp, max_spp, pass_spp, float(threshold), float(floor), dilate,
+                max_depth, seed, None if checkpoint is None else str(checkpoint).encode(),
+                -1.0 if time_limit is None else float(time_limit), mean.ctypes.data_as(_fp), n.ctypes.data_as(_ip),
+                err.ctypes.data_as(_dp), C.byref(st), cb, None)
+        filtered = None
+        if denoise:
+            filtered = np.zeros((H, W, 3), np.float32)
+            dp = denoise_params(validate=False, **(denoise_args or {}))
+            check(load().rt_nw_render_denoised(*args, fspp, C.byref(dp), filtered.ctypes.data_as(_fp)), "rt_nw_render_denoised")
+        else:
+            check(load().rt_nw_render_adaptive(*args), "rt_nw_render_adaptive")
         self._adapt_shape = (H, W)
         if stats is not None:
             stats.update(passes=st.passes, stopped=st.stopped, total_samples=st.total_samples, pixels_at_max=st.pixels_at_max,
                          samples=st.samples, segments=st.segments, active=[int(v) for v in log[:min(st.passes, log.size)]])
         if raised:
             raise raised[0]
-        return mean, n, err
+        return (mean, n, err, filtered) if denoise else (mean, n, err)
 
     def debug_trace(self, cam, W, H, i, j, s, max_depth=50, seed=1984, cap=64, with_time=False):
         """The segments of one camera sample: rows (o.xyz, d.xyz, t, n.xyz) and (winner index, box face);

@@ -513,6 +513,93 @@ int rt_nw_adapt_save(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const
 int rt_nw_adapt_load(rt_nw_ctx *ctx, const char *path, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H,
                      int32_t row0, int32_t row_step, int32_t nrows, int32_t max_depth, uint64_t seed);
 int rt_nw_adapt_info(const char *path, int32_t out8[8], uint64_t out3[3]);
+/* ---- Denoising (DESIGN.md §9 "Denoising") --------------------------------
+ * First-hit feature buffers, a variance guide from the adaptive accumulator
+ * and an edge-avoiding a-trous wavelet filter.  Nothing here changes a render.
+ *
+ * rt_nw_render_features: per pixel, the mean over samples s = 0 .. fspp - 1 of
+ * what the camera ray of sample (i, j, s) meets — segment 0 of
+ * rt_nw_debug_trace(i, j, s), draw for draw, through the walk a render of the
+ * context uses.  8 floats per pixel at (j * W + i) * 8, row 0 at the bottom:
+ *   a.rgb  albedo: the background for a miss, (1, 1, 1) for a dielectric, else
+ *          the texture value of the hit's material (lights and media included);
+ *   n.xyz  the hit record's normal (world space, not flipped); a miss or a
+ *          medium contributes (0, 0, 0), so the mean is NOT a unit vector;
+ *   z      the mean ray parameter t over the samples that hit (0: none did);
+ *   cov    hits / fspp (media count as hits).
+ * Sums are int64 fixed point at 2^-32 per thread (albedo clamped to [0, 64],
+ * normals to [-64, 64] and truncated toward zero, t to [0, 2^20]; NaN -> 0);
+ * a and n are float(double(sum) * 2^-32 / fspp), z float(double(sum_t) * 2^-32
+ * / hits), cov float(double(hits) / fspp).  Either of dev_feat (DEVICE, async
+ * on `stream`) and host_feat (HOST, synchronous) may be null, not both, as
+ * rt_nw_accum_resolve.  Validates as rt_nw_render; RT_EINVAL also for fspp
+ * outside 1..1024 and for W * H >= 2^31. */
+int rt_nw_render_features(rt_nw_ctx *ctx, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t fspp, uint64_t seed,
+                          float *dev_feat, float *host_feat, void *stream);
+/* Host only, pure: the variance of each pixel's mean channel sum r + g + b,
+ * from the moments of rt_nw_adapt_criterion in the same float64 order:
+ *   var = float(max(0, ex2 - mean * mean) / (n - 1)),
+ * which is (err * max(mean, floor))^2 of the criterion; +inf where n < 2. */
+int rt_nw_adapt_variance(const int64_t *sum, const uint64_t *m2, const int32_t *n, int32_t W, int32_t nrows, float *var);
+/* The filter.  Inputs (row-major, any row order as long as all agree):
+ * color W*H*3 per-pixel means; var W*H, the variance of the pixel's mean
+ * channel sum, or null (no luminance term); feat W*H*8 as above.
+ *   prepare: A = max(a, 0.01) per channel (1 without DEMODULATE), Abar = (A.r +
+ *     A.g + A.b) / 3; c' = c / A, v' = var / Abar^2; gz = max(|gx|, |gy|), the
+ *     central difference of z over the in-image neighbours with cov > 0 (one
+ *     missing: the one-sided difference to the pixel itself; both: 0).
+ *   pass k = 0 .. iterations - 1, step = 2^k: taps (dx, dy) in {-2..2}^2 at
+ *     offset step * (dx, dy), those outside the image skipped; h = (1/16, 1/4,
+ *     3/8, 1/4, 1/16);
+ *       w = h(dx) h(dy) exp(-(sigma_n / 2) |n_p - n_q|^2
+ *                           - |z_p - z_q| / (sigma_z gz_p step max(|dx|, |dy|) + 1e-3 |z_p| + 1e-12)
+ *                           - |l_p - l_q| / (sigma_l sqrt(vt_p) + 1e-6)),
+ *     l the channel sum of c', vt_p the 3x3 binomial mean of the pass's input
+ *     v' around p over the in-image pixels whose v' is finite.  The luminance
+ *     term is absent without var and for a centre whose v' is not finite (a
+ *     pixel of fewer than two samples).  The centre tap has w = 9/64.  A tap
+ *     whose colour, v' or weight is not finite is skipped; a centre whose
+ *     colour is not finite passes through unchanged.
+ *       c'_out = sum w c'_q / sum w,  v'_out = sum w^2 v'_q / (sum w)^2
+ *     (v'_out = v'_p where that is not finite).
+ *   finish: out = c' A, var_out = v' Abar^2.
+ * RT_NW_DENOISE_NO_EDGES sets every edge weight to 1: the plain B3 blur, a
+ * test instrument.  The scratch images belong to the context (52 bytes per
+ * pixel, grown on demand, freed by rt_nw_ctx_destroy).  rt_nw_denoise takes
+ * DEVICE arrays and is asynchronous on `stream` (null: the context's);
+ * dev_out may be dev_color.  rt_nw_denoise_host takes HOST arrays and is
+ * synchronous.  p null: the defaults.  RT_EINVAL: iterations outside 1..8, a
+ * sigma that is not finite or <= 0, unknown flag bits, W or H < 1, a null
+ * color, feat or out.  rt_nw_denoise_params_default / _check are host only. */
+#define RT_NW_DENOISE_DEMODULATE 1u
+#define RT_NW_DENOISE_NO_EDGES 2u
+typedef struct rt_nw_denoise_params {
+  int32_t iterations; /* 1..8, default 5 */
+  float sigma_l;      /* default 4 */
+  float sigma_n;      /* default 128 */
+  float sigma_z;      /* default 1 */
+  uint32_t flags;     /* default RT_NW_DENOISE_DEMODULATE */
+} rt_nw_denoise_params;
+int rt_nw_denoise_params_default(rt_nw_denoise_params *p);
+int rt_nw_denoise_params_check(const rt_nw_denoise_params *p);
+int rt_nw_denoise(rt_nw_ctx *ctx, int32_t W, int32_t H, const float *dev_color, const float *dev_var, const float *dev_feat,
+                  const rt_nw_denoise_params *p, float *dev_out, float *dev_var_out, void *stream);
+int rt_nw_denoise_host(rt_nw_ctx *ctx, int32_t W, int32_t H, const float *color, const float *var, const float *feat,
+                       const rt_nw_denoise_params *p, float *out, float *var_out);
+/* The driver: rt_nw_render_adaptive with the same arguments (threshold 0: the
+ * plain render of max_spp), then rt_nw_render_features (fspp samples, `seed`),
+ * rt_nw_adapt_variance of the accumulator and rt_nw_denoise, on the context's
+ * stream.  denoised_out: W*H*3 floats, required.  The other outputs are those
+ * of rt_nw_render_adaptive, bit for bit.  The variance is formed on the host,
+ * as the driver's criterion is: after the render the accumulator is exported
+ * (36 B per pixel), the variance uploaded (4 B per pixel) and a device buffer
+ * of 48 B per pixel allocated for the call and freed after it; none of that
+ * is in the kernel times of profiles/denoise/README.md. */
+int rt_nw_render_denoised(rt_nw_ctx *ctx, rt_nw_scene *scene, const rt_nw_camera *cam, int32_t W, int32_t H, int32_t min_spp,
+                          int32_t max_spp, int32_t pass_spp, double threshold, double floor, int32_t dilate, int32_t max_depth,
+                          uint64_t seed, const char *checkpoint, double time_limit, float *mean_out, int32_t *n_out,
+                          double *err_out, rt_nw_adapt_stats *stats, rt_nw_adapt_on_pass on_pass, void *user, int32_t fspp,
+                          const rt_nw_denoise_params *p, float *denoised_out);
 /* Host only (no device needed): FNV-1a 64 over everything of the scene that
  * can change a pixel, and nothing else — no address, not the accelerator
  * setting, no BVH or grid.  The same value in any process that builds the
