@@ -350,7 +350,7 @@ __device__ __forceinline__ bool path_segment(const SceneView<float> &sc, const S
   else geomk = ACC >= 2 ? lds_sphere(key) : sc.geom[kk];
   const int kind = miss ? -1 : int(sh1k.x);
   float inv_len = 0.0f;
-  if (kind != RT_MAT_LAMBERTIAN) inv_len = drcp(dsqrt(dot<true>(d, d)));
+  if (kind != RT_MAT_LAMBERTIAN) inv_len = drsqrt(dot<true>(d, d));
   if (miss) {
     const V3<float> sk = sky_fast(d, inv_len);
     if constexpr (FIRST) col = sk;
@@ -2954,6 +2954,100 @@ RTMI_EXPORT int rt_debug_exact_math(int32_t which, uint64_t *out) {
   const unsigned long long init[4] = {0, ~0ull, 0, 0};
   HIP_TRY(hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(exact_math_kernel, dim3(1u << 16), dim3(256), 0, nullptr, which, d);  // 2^24 threads x 256
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long v[4];
+  HIP_TRY(hipMemcpy(v, d, sizeof v, hipMemcpyDeviceToHost));
+  (void)hipFree(d);
+  for (int i = 0; i < 4; i++) out[i] = v[i];
+  return RT_OK;
+}
+
+// sqrt_cr for arguments in {+0} U [2^-96, inf) ONLY, without a guard: the max
+// is the identity on [2^-96, inf), and +0 gives g = +0, the residual
+// fma(-0, 0, +0) = +0 and the root +0 = sqrtf(+0).  Any other input (-0,
+// denormals, small normals, negatives, inf, NaN) is outside its contract: the
+// max would swallow a NaN.  Exact, and the sampling roots' arguments (unit_dir,
+// scatter_fast, in_disk_direct) lie in its domain for all 2^24 uniforms, but
+// the render kernel is no faster for it (profiles/README.md, measured and
+// not kept): it lives here for the checks below and is not in the render path.
+__device__ __forceinline__ float sqrt_cr_zero_or_big(float x) {
+  const float y = __builtin_amdgcn_rsqf(__builtin_fmaxf(x, 0x1p-96f));
+  const float g = x * y, h = 0.5f * y;
+  return __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
+}
+
+// Exhaustive checks of the guard forms of rtmi_path.h (rsqrt_cr, rcp_cr's
+// unsigned range test) and of sqrt_cr_zero_or_big in exact_math_kernel's
+// launch shape, results compared by bit pattern with NaN == NaN:
+//  form 0  rsqrt_cr(x) against 1.0f / sqrtf(x), all 2^32 inputs
+//  form 1  rcp_cr(x) against 1.0f / x, all 2^32 inputs
+//  form 2  sqrt_cr_zero_or_big(x) against sqrtf(x) on its domain, the bit
+//          patterns of {+0} U [2^-96, inf); the rest is skipped
+//  form 3  the sampling roots' two arguments, fma(-z, z, 1) with
+//          z = fma(-2, u, 1) and u itself, for the 2^24 uniforms u = k 2^-24
+//          (one per thread): the argument must lie in form 2's domain and
+//          sqrt_cr_zero_or_big must equal sqrt_cr there ("input" = k, or
+//          k | 2^24 for the second argument)
+//  form 4  a probe, no product code: sqrt_cr's short form with no guard at
+//          all against sqrtf(x) on the small normals [2^-126, 2^-96)
+// res[0] mismatches, res[1] the smallest mismatching input, res[2] the two
+// results there (got | IEEE << 32), res[3] how many inputs were compared.
+__device__ __forceinline__ bool in_zero_or_big(uint32_t bits) { return bits == 0 || (bits >= 0x0F800000u && bits < 0x7F800000u); }
+template <int FORM> __global__ void math_guards_kernel(unsigned long long *res) {
+  const uint32_t tid = uint32_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  unsigned bad = 0, compared = 0;
+  uint32_t first = 0xFFFFFFFFu, got_first = 0, want_first = 0;
+  for (uint32_t k = 0; k < (FORM == 3 ? 2u : 256u); ++k) {
+    uint32_t bits = (tid << 8) + k, in = bits;
+    bool same = true;
+    if constexpr (FORM == 3) {
+      const float u = float(tid) * 0x1p-24f, z = __builtin_fmaf(-2.0f, u, 1.0f);
+      bits = __float_as_uint(k == 0 ? __builtin_fmaf(-z, z, 1.0f) : u);
+      in = tid | (k << 24);
+      same = in_zero_or_big(bits);
+    } else if constexpr (FORM == 2) {
+      if (!in_zero_or_big(bits)) continue;
+    } else if constexpr (FORM == 4) {
+      if (bits < 0x00800000u || bits >= 0x0F800000u) continue;
+    }
+    const float x = __uint_as_float(bits);
+    float got, want;
+    if constexpr (FORM == 0) got = rsqrt_cr(x), want = 1.0f / __builtin_sqrtf(x);
+    else if constexpr (FORM == 1) got = rcp_cr(x), want = 1.0f / x;
+    else if constexpr (FORM == 2) got = sqrt_cr_zero_or_big(x), want = __builtin_sqrtf(x);
+    else if constexpr (FORM == 3) got = sqrt_cr_zero_or_big(x), want = sqrt_cr(x);
+    else {
+      const float y = __builtin_amdgcn_rsqf(x), g = x * y;
+      got = __builtin_fmaf(__builtin_fmaf(-g, g, x), 0.5f * y, g), want = __builtin_sqrtf(x);
+    }
+    ++compared;
+    same = same && (__float_as_uint(got) == __float_as_uint(want) || (got != got && want != want));
+    if (!same) {
+      ++bad;
+      if (in < first) { first = in; got_first = __float_as_uint(got); want_first = __float_as_uint(want); }
+    }
+  }
+  if (compared) atomicAdd(&res[3], (unsigned long long)compared);
+  if (bad) {
+    atomicAdd(&res[0], (unsigned long long)bad);
+    const unsigned long long old = atomicMin(&res[1], (unsigned long long)first);
+    if (first < old) res[2] = got_first | (unsigned long long)want_first << 32;  // (racy only between mismatching threads)
+  }
+}
+
+RTMI_EXPORT int rt_debug_math_guards(int32_t form, uint64_t *out) {
+  if (!out || form < 0 || form > 4) return set_error(RT_EINVAL, "rt_debug_math_guards: bad argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(RT_ENODEVICE, "no GPU");
+  unsigned long long *d = nullptr;
+  int rc;
+  if ((rc = dev_alloc(&d, 4))) return rc;
+  const unsigned long long init[4] = {0, ~0ull, 0, 0};
+  HIP_TRY(hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice));
+  void (*const kern[5])(unsigned long long *) = {math_guards_kernel<0>, math_guards_kernel<1>, math_guards_kernel<2>,
+                                                 math_guards_kernel<3>, math_guards_kernel<4>};
+  hipLaunchKernelGGL(kern[form], dim3(1u << 16), dim3(256), 0, nullptr, d);  // 2^24 threads
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long v[4];

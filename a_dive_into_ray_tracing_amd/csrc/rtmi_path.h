@@ -58,7 +58,12 @@ template <bool F> __device__ __forceinline__ double madd(double a, double b, dou
 //  range test on the bit pattern.
 //  reciprocal: v_rcp_f32, then one Newton step with exact fma residual; the
 //  ranges where 1/x or x lies outside the normal range keep the IEEE
-//  division (a branch no realistic scene takes).
+//  division (a branch no realistic scene takes) — one unsigned range test on
+//  the bit pattern shifted left by one, the same set of inputs for both signs
+//  as |x| >= 2^-125 && |x| <= 2^125.
+//  1 / sqrt: rsqrt_cr runs both sequences under sqrt_cr's test alone (the
+//  root of an in-range x is always in rcp_cr's range); all 2^32 inputs of
+//  both are checked by rt_debug_math_guards (tests/test_math_guards.py).
 // (The out-of-range inputs take the IEEE form behind a wave-uniform branch on
 // their ballot: the common path pays one compare and a scalar branch, not an
 // exec-mask save/restore — DESIGN.md §4.5.)
@@ -74,8 +79,10 @@ __device__ __forceinline__ float sqrt_cr(float x) {
   return r;
 }
 __device__ __forceinline__ float rcp_cr(float x) {
-  const float ax = __builtin_fabsf(x);
-  const bool slow = !(ax >= 0x1p-125f && ax <= 0x1p+125f);  // zero, denormal, huge, inf, NaN
+  // |x| in [2^-125, 2^125] by one unsigned test: the bit pattern shifted left
+  // by one drops the sign, the constants are twice bits(2^-125) and
+  // bits(2^125); zero and denormals wrap above the span, inf and NaN lie above
+  const bool slow = (__float_as_uint(x) << 1) - 0x02000000u > 0xFC000000u - 0x02000000u;
   const float r0 = __builtin_amdgcn_rcpf(x);
   float r = __builtin_fmaf(__builtin_fmaf(-x, r0, 1.0f), r0, r0);
   if (__builtin_expect(__ballot(slow) != 0, 0)) {
@@ -83,10 +90,27 @@ __device__ __forceinline__ float rcp_cr(float x) {
   }
   return r;
 }
+// 1 / sqrt(x) = rcp_cr(sqrt_cr(x)) under sqrt_cr's guard alone: for x in
+// [2^-96, inf) the root lies in [2^-48, 2^64), inside rcp_cr's fast range, so
+// the second guard's answer is known.
+__device__ __forceinline__ float rsqrt_cr(float x) {
+  const bool slow = __float_as_uint(x) - 0x0F800000u >= 0x7F800000u - 0x0F800000u;
+  const float y = __builtin_amdgcn_rsqf(x);
+  const float g = x * y, h = 0.5f * y;
+  const float s = __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
+  const float r0 = __builtin_amdgcn_rcpf(s);
+  float r = __builtin_fmaf(__builtin_fmaf(-s, r0, 1.0f), r0, r0);
+  if (__builtin_expect(__ballot(slow) != 0, 0)) {
+    if (slow) r = 1.0f / __builtin_sqrtf(x);
+  }
+  return r;
+}
 __device__ __forceinline__ float dsqrt(float x) { return sqrt_cr(x); }
 __device__ __forceinline__ float drcp(float x) { return rcp_cr(x); }
+__device__ __forceinline__ float drsqrt(float x) { return rsqrt_cr(x); }
 __device__ __forceinline__ double dsqrt(double x) { return __builtin_sqrt(x); }
 __device__ __forceinline__ double drcp(double x) { return 1.0 / x; }
+__device__ __forceinline__ double drsqrt(double x) { return 1.0 / __builtin_sqrt(x); }
 __device__ __forceinline__ float dfabs(float x) { return __builtin_fabsf(x); }
 __device__ __forceinline__ double dfabs(double x) { return __builtin_fabs(x); }
 __device__ __forceinline__ float dfmin(float a, float b) { return __builtin_fminf(a, b); }
@@ -103,7 +127,7 @@ template <bool F, class R> __device__ __forceinline__ R dot(V3<R> a, V3<R> b) {
 template <class R> __device__ __forceinline__ V3<R> scale(R t, V3<R> v) { return mk(t * v.x, t * v.y, t * v.z); }
 // unit_vector vec3.h:101 (operator/ is (1/t)*v, vec3.h:89)
 template <bool F, class R> __device__ __forceinline__ V3<R> unit(V3<R> v) {
-  return scale(drcp(dsqrt(dot<F>(v, v))), v);
+  return scale(drsqrt(dot<F>(v, v)), v);
 }
 // reflect vec3.h:114
 template <bool F, class R> __device__ __forceinline__ V3<R> reflect(V3<R> v, V3<R> n) {
@@ -1300,7 +1324,7 @@ __device__ __forceinline__ V3<float> sky_fast(V3<float> d, float inv_len) {
   return mk(__builtin_fmaf(t, 0.5f, 1.0f - t), __builtin_fmaf(t, 0.7f, 1.0f - t), __builtin_fmaf(t, 1.0f, 1.0f - t));
 }
 template <bool F, class R> __device__ __forceinline__ V3<R> sky(V3<R> d) {
-  const R uy = drcp(dsqrt(dot<F>(d, d))) * d.y;
+  const R uy = drsqrt(dot<F>(d, d)) * d.y;
   const R t = R(0.5) * (uy + R(1));
   return mk(madd<F>(t, R(0.5), R(1) - t), madd<F>(t, R(0.7), R(1) - t), madd<F>(t, R(1), R(1) - t));
 }
