@@ -481,8 +481,28 @@ __global__ __launch_bounds__(64 * GridShape<ACC != 0>::waves, GridShape<ACC != 0
         if (pass && slot < cap) tl[slot] = uint16_t(key);
         n = __builtin_amdgcn_readfirstlane(n + __popcll(m));
       }
+      // The big spheres by the same test, one more round (lane j: big slot j,
+      // whose key is j): the ones that pass go behind the small ones when the
+      // wave's 32 entries hold them all, and the list is then complete
+      // (kTileBigFlag: its batches run no hit_big).  The acceptance is
+      // order-independent, so where in the list they stand does not matter.
+      int flag = 0;
+      if (n <= cap && a.acc.ntile_big > 0) {
+        const float4 *const big = a.acc.tile_sph + a.acc.ntile + (a.acc.ntile + 3) / 4;
+        bool pass = false;
+        if (ln < a.acc.ntile_big) {
+          const float4 s = big[ln];
+          pass = tile_may_hit(tb, s.x, s.y, s.z, s.w);
+        }
+        const unsigned long long m = __ballot(pass);
+        if (n + __popcll(m) <= kTileListCap) {
+          if (pass) tl[n + int(__builtin_amdgcn_mbcnt_lo(unsigned(m), 0u))] = uint16_t(ln);
+          n = __builtin_amdgcn_readfirstlane(n + __popcll(m));
+          flag = kTileBigFlag;
+        }
+      }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the wave's other lanes read the list
-      if (n <= cap) tile_list = __builtin_amdgcn_readfirstlane(int(lds_address(tl) << 6) | n);
+      if (flag || n <= cap) tile_list = __builtin_amdgcn_readfirstlane(int(lds_address(tl) << 6) | n | flag);
     }
   }
 
@@ -1436,6 +1456,10 @@ struct rt_ctx {
   int32_t tile_list_max = std::getenv("RTMI_TILE_LIST_MAX")
                               ? std::max(0, std::min(kTileListCap, std::atoi(std::getenv("RTMI_TILE_LIST_MAX"))))
                               : kTileListCap;
+  // Accel::ntile_big, and RTMI_TILE_BIG=0 (A/B and tests): the lists name no
+  // big spheres, every batch runs hit_big
+  int32_t ntile_big = 0;
+  bool tile_big = !(std::getenv("RTMI_TILE_BIG") && std::atoi(std::getenv("RTMI_TILE_BIG")) == 0);
   // RTMI_GRID_GLOBAL=1 (tests): the global-memory walk for any grid
   bool force_grid_global = std::getenv("RTMI_GRID_GLOBAL") && std::atoi(std::getenv("RTMI_GRID_GLOBAL")) != 0;
   // cost-ordered dispatch: per-tile world.hit counts of the
@@ -1724,9 +1748,11 @@ struct GridBuild {
   // record slot of it / 16; empty when a slot number passes 16 bits
   std::vector<float4> tile_sph;
   std::vector<uint32_t> tile_keys;
+  // the same per big slot (Accel::ntile_big); empty for more than kTileBigMax
+  std::vector<float4> tile_big;
 };
-bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, int32_t n, int32_t nbig_slots,
-                GridBuild &out) {
+bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, const std::vector<int32_t> &big, int32_t n,
+                int32_t nbig_slots, GridBuild &out) {
   if (n > 65535) return false;  // references are 16-bit scene indices
   const char *env = std::getenv("RTMI_GRID_CELLS");
   // 0.3 cells per sphere: config 2 33.3 ms (0.2: 33.3, 0.5: 33.6, 1: 34.5,
@@ -1823,6 +1849,21 @@ bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, int32_t 
       out.tile_sph.push_back(make_float4(float(c[0]), float(c[1]), float(c[2]), rg));
       out.tile_keys.push_back(first[size_t(k)]);
     }
+    // The big slots by the same rule on the sphere's own scale: 1e-3 of its
+    // radius — 1 unit on the R = 1000 ground, where the cells' margin, which
+    // counts the centre's distance too, gives 2 and lifts the horizon over
+    // another 6 % of config 2's tiles — and 1e-5 of its centre's coordinates,
+    // 100 times their float spacing, which is what the centre's rounding and
+    // tile_may_hit's differences from it can be off by (on the ground 1e-4).
+    if (big.size() <= size_t(kTileBigMax))
+      for (int32_t k : big) {  // ascending scene index: slot order
+        const double *c = b.cr + 4 * k;
+        const double cmax = std::max(std::max(std::fabs(c[0]), std::fabs(c[1])), std::fabs(c[2]));
+        const double R = std::fabs(c[3]) + 1e-3 * (1.0 + std::fabs(c[3])) + 1e-5 * cmax + b.margin_scene;
+        float rg = float(R);
+        if (double(rg) < R) rg = std::nextafter(rg, INFINITY);
+        out.tile_big.push_back(make_float4(float(c[0]), float(c[1]), float(c[2]), rg));
+      }
   }
   return true;
 }
@@ -1985,7 +2026,7 @@ RTMI_EXPORT int rt_ctx_set_scene(rt_ctx *ctx, const rt_scene *scene) {
     // uniform grid over the same small spheres
     ctx->grid_ok = false;
     GridBuild gb;
-    if (!small.empty() && build_grid(b, small, n, nb_pad, gb)) {
+    if (!small.empty() && build_grid(b, small, big, n, nb_pad, gb)) {
       if ((rc = dev_alloc(&ctx->grid_sph, gb.sph.size())) || (rc = dev_alloc(&ctx->grid_cells, gb.cells.size())) ||
           (rc = dev_alloc(&ctx->grid_refs, std::max<size_t>(gb.refs.size(), 1))))
         return rc;
@@ -1998,13 +2039,16 @@ RTMI_EXPORT int rt_ctx_set_scene(rt_ctx *ctx, const rt_scene *scene) {
       ctx->grid.refs = ctx->grid_refs;
       ctx->ngrid_sph = int32_t(gb.sph.size());
       ctx->grid_global = ctx->force_grid_global || !gb.fits_lds;
-      ctx->ntile = 0;
+      ctx->ntile = ctx->ntile_big = 0;
       if (!ctx->grid_global && !gb.tile_sph.empty()) {
-        // {centre, grown radius} per small sphere, then the slot keys
-        const size_t ns = gb.tile_sph.size();
-        std::vector<float4> tab(ns + (ns + 3) / 4);
+        // {centre, grown radius} per small sphere, then the slot keys, then
+        // {centre, grown radius} per big slot
+        const size_t ns = gb.tile_sph.size(), nk = (ns + 3) / 4, nb = ctx->tile_big ? gb.tile_big.size() : 0;
+        std::vector<float4> tab(ns + nk + nb);
         std::copy(gb.tile_sph.begin(), gb.tile_sph.end(), tab.begin());
         std::memcpy(tab.data() + ns, gb.tile_keys.data(), ns * sizeof(uint32_t));
+        std::copy(gb.tile_big.begin(), gb.tile_big.begin() + nb, tab.begin() + ns + nk);
+        ctx->ntile_big = int32_t(nb);
         if ((rc = dev_alloc(&ctx->tile_sph, tab.size()))) return rc;
         HIP_TRY(hipMemcpy(ctx->tile_sph, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
         ctx->ntile = int32_t(ns);
@@ -2061,7 +2105,7 @@ RTMI_EXPORT int rt_debug_grid_strides(const int32_t *n3, uint32_t *strides2) {
 namespace {
 // The grid rt_ctx_set_scene builds for a scene, on the host alone (false: the
 // scene has none); nbs: the big spheres' record slots before the cells'
-bool host_grid(const rt_scene *scene, GridBuild &gb, int32_t &nbs) {
+bool host_grid(const rt_scene *scene, GridBuild &gb, int32_t &nbs, std::vector<int32_t> *big_out = nullptr) {
   const int n = scene->n;
   std::vector<float4> g(n, make_float4(0.f, 0.f, 0.f, 0.f));  // (build_grid copies the records; their values do not shape the grid)
   std::vector<double> rad(n);
@@ -2077,7 +2121,8 @@ bool host_grid(const rt_scene *scene, GridBuild &gb, int32_t &nbs) {
   }
   BvhBuilder b{scene->center_radius, g, 1e-6 * scale, {}, {}, {}};
   nbs = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
-  return !small.empty() && build_grid(b, small, n, nbs, gb);
+  if (big_out) *big_out = big;  // the big slots' scene indices
+  return !small.empty() && build_grid(b, small, big, n, nbs, gb);
 }
 }  // namespace
 
@@ -2174,6 +2219,44 @@ RTMI_EXPORT int rt_debug_tile_list(const rt_scene *scene, const rt_camera *camer
   return RT_OK;
 }
 
+// The same for the big spheres (the same host code; rt_debug_tile_list stays
+// the small spheres alone): the big spheres the kernel appends to the tile's
+// list, as scene indices in out_indices[kTileBigMax] per tile and their number
+// in out_count.  A count of -1 for every tile: the scene has more than
+// kTileBigMax big spheres and its lists name none (every batch runs hit_big).
+// (The kernel appends them where the tile has a list and the list's 32
+// entries hold both; RTMI_TILE_BIG is not read here.)
+RTMI_EXPORT int rt_debug_tile_big(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
+                                  int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t *out_indices,
+                                  int32_t *out_count) {
+  if (!scene || scene->n <= 0 || !scene->center_radius || !camera || !out_indices || !out_count)
+    return set_error(RT_EINVAL, "rt_debug_tile_big: bad argument");
+  if (W < 2 || H < 2 || row0 < 0 || row0 >= H || row_step < 1 || nrows < 1 ||
+      (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64))
+    return set_error(RT_EINVAL, "rt_debug_tile_big: bad image, strip or tile shape");
+  const int32_t nvalid = int32_t(std::min<int64_t>(nrows, (int64_t(H) - row0 + row_step - 1) / row_step));
+  const int32_t tw = tile_w ? tile_w : auto_tile_w(W, nvalid), th = 64 / tw;
+  const int64_t tiles = int64_t((W + tw - 1) / tw) * ((nvalid + th - 1) / th);
+  if (tile < -1 || tile >= tiles) return set_error(RT_EINVAL, "rt_debug_tile_big: tile %d of %lld", tile, (long long)tiles);
+  GridBuild gb;
+  int32_t nbs;
+  std::vector<int32_t> big;
+  if (!host_grid(scene, gb, nbs, &big) || gb.tile_sph.empty()) return set_error(RT_EUNSUPPORTED, "no tile lists for this scene");
+  const bool none = big.size() > size_t(kTileBigMax);
+  const Cam<float> cam = cam_f(camera);
+  for (int64_t t = tile < 0 ? 0 : tile, o = 0; t < (tile < 0 ? tiles : tile + 1); ++t, ++o) {
+    int32_t x0, vw, j_lo, j_hi, cnt = 0;
+    tile_extent(W, row0, row_step, nvalid, tw, int32_t(t), x0, vw, j_lo, j_hi);
+    const TileBundle tb = tile_bundle(cam, W, H, x0, vw, j_lo, j_hi);
+    for (size_t i = 0; i < gb.tile_big.size(); ++i) {
+      const float4 s = gb.tile_big[i];
+      if (tile_may_hit(tb, s.x, s.y, s.z, s.w)) out_indices[o * kTileBigMax + cnt++] = big[i];
+    }
+    out_count[o] = none ? -1 : cnt;
+  }
+  return RT_OK;
+}
+
 RTMI_EXPORT int rt_ctx_set_tuning(rt_ctx *ctx, int32_t tile_w, int32_t chunk) {
   if (!ctx) return set_error(RT_EINVAL, "null ctx");
   if (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64)
@@ -2211,6 +2294,7 @@ Accel accel_of(const rt_ctx *ctx, int kind) {
     a.grid_gmem = ctx->grid_global ? ctx->grid_gmem : nullptr;
     a.tile_sph = ctx->tile_sph;
     a.ntile = kind <= 3 ? ctx->ntile : 0;
+    a.ntile_big = kind <= 3 ? ctx->ntile_big : 0;
   }
   return a;
 }

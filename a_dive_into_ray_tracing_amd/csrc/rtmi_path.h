@@ -525,6 +525,11 @@ struct Accel {
   // record) as its offset from the first slot / 16.  ntile 0: no lists.
   const float4 *tile_sph;
   int32_t ntile;
+  // the big slots' {centre, grown radius}, slot order, behind the keys (at
+  // tile_sph + ntile + (ntile + 3) / 4): a tile's list then names the big
+  // spheres its camera rays can meet as well, and its batches skip hit_big.
+  // 0: no such table (more than kTileBigMax big spheres, RTMI_TILE_BIG=0)
+  int32_t ntile_big;
 };
 
 // ---------------------------------------------------------------------------
@@ -545,6 +550,15 @@ struct TileBundle {
 };
 constexpr int kTileListCap = 32;      // entries of a wave's list (16 bits each)
 constexpr int kTileListMinSpp = 4;    // items of fewer samples build no list (the 1-spp cost probe)
+// Big spheres in the lists: a scene of at most kTileBigMax big spheres has
+// them tested against the tile's bundle too (one more round of the build), and
+// the ones that pass are appended to the tile's list as their record slots'
+// keys (slot j's is j).  kTileBigFlag in the tile_list value says so: the list
+// then names every sphere a camera ray of the tile can meet, and the batch
+// runs no hit_big.  The value's bits: 0-5 the length, 6-21 the LDS address
+// (below 2^16), 30 the flag.
+constexpr int kTileBigMax = 8;
+constexpr int32_t kTileBigFlag = 1 << 30;
 
 // The tile of columns [x0, x0 + vw) and image rows j_lo .. j_hi (a strip's
 // rows lie row_step apart: any rows between them are covered too).  The
@@ -902,18 +916,23 @@ __device__ __forceinline__ int32_t hit_world_grid(const Accel &acc_s, V3<float> 
   };
   float t_max = INFINITY;
   int32_t best_a = -1;  // the hit's record-slot key; -1: no hit yet
-  hit_big<GP, true, GMEM>(acc_s, d, K, a, aL, mx, my, mz, inv_a, t_max, best_a
+  // (a list that names the big spheres too, kTileBigFlag: they are tested
+  // with the list, by the same FMA chains on the same {c, S} — the big slots'
+  // records — and resolve_key's tie rule through the slot index table, which
+  // on the big slots, in scene order, is hit_big's)
+  if (!(LIST && tile_list >= 0 && (tile_list & kTileBigFlag)))
+    hit_big<GP, true, GMEM>(acc_s, d, K, a, aL, mx, my, mz, inv_a, t_max, best_a
 #if RTMI_STATS
-              , gstats
+                , gstats
 #endif
-              );
+                );
 #if RTMI_TRACE_PHASES
   const unsigned long long tp1 = __builtin_amdgcn_s_memtime();
   pc.c[0] += tp1 - tp0;
   unsigned long long tp2 = tp1;
 #endif
   if (LIST && tile_list >= 0) {
-    const uint32_t tl = uint32_t(tile_list) >> 6, tl_end = tl + 2u * (uint32_t(tile_list) & 63u);
+    const uint32_t tl = (uint32_t(tile_list) >> 6) & 0xFFFFu, tl_end = tl + 2u * (uint32_t(tile_list) & 63u);
     for (uint32_t e = tl; e < tl_end; e += 2u) {
       // the key made scalar: the record's address is the same in every lane
       const uint32_t key = base + 16u * uint32_t(__builtin_amdgcn_readfirstlane(int(lds_u16(e))));
