@@ -156,7 +156,7 @@ def device_count():
 
 
 def auto_tile_w(W, rows):
-    """The tile width `rt_render_rows` picks when tile_w is 0 (rtmi_device.hip
+    """The tile width `rt_render_rows` picks when tile_w is 0 (csrc/rtmi_accel.h
     auto_tile_w): 8 unless 16x4 tiles leave fewer idle lanes in partial tiles."""
     def idle(tw):
         th = 64 // tw

@@ -1,5 +1,8 @@
 // rtmi_device.hip — device half of librtmi.so: the gfx950 path-tracing
-// kernels and the C-ABI entry points that launch them.
+// kernels and the C-ABI entry points that launch them.  What a scene's
+// structures hold is built on the CPU by rtmi_accel_build.cpp (build_accel,
+// the rt_debug_grid_* / rt_debug_tile_* entry points); rt_ctx_set_scene here
+// decides LDS residency and uploads.
 //
 // Hot path: the per-pixel sample loop of the
 // reference — camera ray (camera.h:56-62), the iterative ray_color bounce
@@ -1531,17 +1534,6 @@ struct DeviceGuard {
   }
 };
 
-Cam<float> cam_f(const rt_camera *c) {
-  auto v = [](const double *p) { return mk(float(p[0]), float(p[1]), float(p[2])); };
-  return Cam<float>{v(c->origin), v(c->lower_left_corner), v(c->horizontal), v(c->vertical), v(c->u), v(c->v),
-                    float(c->lens_radius)};
-}
-Cam<double> cam_d(const rt_camera *c) {
-  auto v = [](const double *p) { return mk(p[0], p[1], p[2]); };
-  return Cam<double>{v(c->origin), v(c->lower_left_corner), v(c->horizontal), v(c->vertical), v(c->u), v(c->v),
-                     c->lens_radius};
-}
-
 template <class T> int dev_alloc(T **p, size_t count) {
   if (*p) (void)hipFree(*p);
   *p = nullptr;
@@ -1626,259 +1618,42 @@ RTMI_EXPORT int rt_ctx_destroy(rt_ctx *ctx) {
 namespace {
 constexpr size_t kBvhLdsMax = 64 * 1024;  // BVH bytes staged per block
 
-// BVH over the small spheres: binary, SAH split (full sweep of the sorted
-// centroids on each axis: the split minimising area(L)*|L| + area(R)*|R|),
-// leaves of <= kLeafMax spheres, nodes in DFS order with skip links.  Boxes
-// are the spheres' double-precision bounds, each grown by its own margin (1e-3
-// of the sphere's coordinate scale, ~100x the float error of its hit test,
-// plus 1e-6 of the scene's) and rounded outward to half precision, so every
-// sphere the float test can report lies strictly inside its leaf's box.
-uint16_t half_bits(_Float16 h) { return __builtin_bit_cast(uint16_t, h); }
-// largest half <= v (-inf below the half range)
-uint16_t half_down(double v) {
-  _Float16 h = _Float16(v);
-  while (double(h) > v) {
-    uint16_t b = half_bits(h);
-    if (b == 0x0000) b = 0x8001;          // +0 -> -min denormal
-    else if (b & 0x8000) b = uint16_t(b + 1);  // negative: away from zero
-    else b = uint16_t(b - 1);             // positive: toward zero
-    h = __builtin_bit_cast(_Float16, b);
+// Sphere pairs of the packed loops: slot s holds the record g[slot ? slot[s] : s],
+// or the never-hit dummy for a negative slot[s] and for the slots from nfilled
+// to nslots (even), plus kPairGroup pairs of prefetch padding
+std::vector<SpherePair> pack_pairs(const Rec4 *g, const int32_t *slot, size_t nfilled, size_t nslots) {
+  std::vector<SpherePair> pr(nslots / 2 + kPairGroup);
+  for (auto &p : pr) {
+    p.cx = f2v{0.f, 0.f}; p.cy = f2v{0.f, 0.f}; p.cz = f2v{0.f, 0.f}; p.S = f2v{kDummyS, kDummyS};
   }
-  return half_bits(h);
+  for (size_t s = 0; s < nfilled; s++) {
+    const int64_t k = slot ? slot[s] : int64_t(s);
+    if (k < 0) continue;
+    SpherePair &p = pr[s / 2];
+    const int h = int(s & 1);
+    p.cx[h] = g[k].x; p.cy[h] = g[k].y; p.cz[h] = g[k].z; p.S[h] = g[k].w;
+  }
+  return pr;
 }
-uint16_t half_up(double v) { return uint16_t(half_down(-v) ^ 0x8000); }
 
-struct BvhBuilder {
-  const double *cr;
-  const std::vector<float4> &g;
-  double margin_scene;  // 1e-6 of the whole scene's scale (rays from far away)
-  std::vector<BvhNode> nodes;
-  std::vector<float4> sph;
-  std::vector<int32_t> idx;
-
-  struct Box {
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    void add(const double *c, double rr) {
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = std::min(lo[a], c[a] - rr);
-        hi[a] = std::max(hi[a], c[a] + rr);
-      }
-    }
-    double area() const {
-      const double e0 = hi[0] - lo[0], e1 = hi[1] - lo[1], e2 = hi[2] - lo[2];
-      return e0 * e1 + e1 * e2 + e0 * e2;
-    }
-  };
-  // sphere k's box margin: 1e-3 of its own coordinate scale (~100x the float
-  // error of its hit test) + margin_scene
-  double margin(int32_t k) const {
-    const double *c = cr + 4 * k;
-    const double own = std::max(std::max(std::fabs(c[0]), std::fabs(c[1])), std::fabs(c[2])) + std::fabs(c[3]);
-    return 1e-3 * (1.0 + own) + margin_scene;
+// The uploads of one rt_ctx_set_scene: upload() allocates a buffer and queues
+// its copy, copy_all() runs the copies once every buffer is allocated (a
+// hipFree between two copies would wait for the first)
+struct Uploads {
+  struct Copy { void *dst; const void *src; size_t bytes; };
+  std::vector<Copy> copies;
+  template <class T, class V> int upload(T **p, const V &v, size_t count) {
+    static_assert(sizeof(T) == sizeof(v[0]), "host and device element sizes");
+    if (int rc = dev_alloc(p, count)) return rc;
+    if (count) copies.push_back(Copy{*p, v.data(), count * sizeof(T)});
+    return RT_OK;
   }
-  Box bounds(const int32_t *ids, int cnt) const {
-    Box b;
-    for (int i = 0; i < cnt; ++i) b.add(cr + 4 * ids[i], std::fabs(cr[4 * ids[i] + 3]) + margin(ids[i]));
-    return b;
-  }
-  void sort_axis(int32_t *ids, int cnt, int ax) const {
-    std::sort(ids, ids + cnt, [&](int32_t x, int32_t y) {
-      const double cx = cr[4 * x + ax], cy = cr[4 * y + ax];
-      return cx < cy || (cx == cy && x < y);
-    });
-  }
-  void build(int32_t *ids, int cnt) {
-    const int me = int(nodes.size());
-    nodes.push_back(BvhNode{});
-    const Box bb = bounds(ids, cnt);
-    BvhNode nd{};
-    nd.x = uint32_t(half_down(bb.lo[0])) | uint32_t(half_up(bb.hi[0])) << 16;
-    nd.y = uint32_t(half_down(bb.lo[1])) | uint32_t(half_up(bb.hi[1])) << 16;
-    nd.z = uint32_t(half_down(bb.lo[2])) | uint32_t(half_up(bb.hi[2])) << 16;
-    if (cnt <= kLeafMax) {
-      nd.link = ~((int32_t(sph.size()) << 4) | cnt);
-      for (int i = 0; i < cnt; ++i) {
-        sph.push_back(g[ids[i]]);
-        idx.push_back(ids[i]);
-      }
-    } else {
-      // SAH sweep: prefix/suffix boxes over the centroid order of each axis
-      double best = INFINITY;
-      int best_ax = 0, best_mid = cnt / 2;
-      std::vector<double> left_cost(cnt);
-      for (int ax = 0; ax < 3; ++ax) {
-        sort_axis(ids, cnt, ax);
-        Box l;
-        for (int i = 1; i < cnt; ++i) {
-          l.add(cr + 4 * ids[i - 1], std::fabs(cr[4 * ids[i - 1] + 3]) + margin(ids[i - 1]));
-          left_cost[i] = l.area() * i;
-        }
-        Box r;
-        for (int i = cnt - 1; i >= 1; --i) {
-          r.add(cr + 4 * ids[i], std::fabs(cr[4 * ids[i] + 3]) + margin(ids[i]));
-          const double c = left_cost[i] + r.area() * (cnt - i);
-          if (c < best) { best = c; best_ax = ax; best_mid = i; }
-        }
-      }
-      sort_axis(ids, cnt, best_ax);
-      build(ids, best_mid);
-      build(ids + best_mid, cnt - best_mid);
-      nd.link = int32_t(nodes.size());
-    }
-    nodes[me] = nd;
+  template <class T, class V> int upload(T **p, const V &v) { return upload(p, v, v.size()); }
+  int copy_all() const {
+    for (const Copy &c : copies) HIP_TRY(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice));
+    return RT_OK;
   }
 };
-}  // namespace
-
-namespace {
-// Uniform grid over the small spheres.  The box of their
-// margin-grown boxes (the BVH's margins) is cut into cells of about
-// RTMI_GRID_CELLS (default 0.3) cells per sphere, as near cubic as the box
-// allows (the final scene's thin layer of spheres: 30 x 1 x 30 cells); every
-// sphere is listed in every cell its grown box overlaps.  Cell boundaries are
-// the float values g0 + c*h the device computes, so host and device agree to
-// a rounding error far below the margins.
-struct GridBuild {
-  GridDesc desc{};
-  std::vector<float4> sph;     // every sphere of the scene by scene index
-  std::vector<uint32_t> cells;  // ncells + 1: each cell's first reference
-  std::vector<uint32_t> refs;   // 16 x scene index
-  bool fits_lds = true;         // its LDS image fits the per-block budget (else: walked in global memory)
-  // tile lists (Accel::tile_sph): per small sphere {centre, grown radius} and a
-  // record slot of it / 16; empty when a slot number passes 16 bits
-  std::vector<float4> tile_sph;
-  std::vector<uint32_t> tile_keys;
-  // the same per big slot (Accel::ntile_big); empty for more than kTileBigMax
-  std::vector<float4> tile_big;
-};
-bool build_grid(const BvhBuilder &b, const std::vector<int32_t> &small, const std::vector<int32_t> &big, int32_t n,
-                int32_t nbig_slots, GridBuild &out) {
-  if (n > 65535) return false;  // references are 16-bit scene indices
-  const char *env = std::getenv("RTMI_GRID_CELLS");
-  // 0.3 cells per sphere: config 2 33.3 ms (0.2: 33.3, 0.5: 33.6, 1: 34.5,
-  // 2: 35.2, 4: 38.0; round 2) and, on the record slots, 19.30 ms (0.2:
-  // 19.38, 0.25: 19.33, 0.4: 19.33; profiles/r04/grid_density.txt)
-  const double per_sphere = env && std::atof(env) > 0 ? std::atof(env) : 0.3;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int32_t k : small) {
-    const double *c = b.cr + 4 * k, R = std::fabs(c[3]) + b.margin(k);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = std::min(lo[a], c[a] - R);
-      hi[a] = std::max(hi[a], c[a] + R);
-    }
-  }
-  double e[3], vol = 1;
-  for (int a = 0; a < 3; ++a) {
-    e[a] = std::max(hi[a] - lo[a], 1e-6 * (1 + std::fabs(lo[a])));
-    vol *= e[a];
-  }
-  const double cell = std::cbrt(vol / (per_sphere * double(small.size())));
-  // analysis knob: RTMI_GRID_ASPECT = x-cell / z-cell size ratio (1: cubic)
-  const char *asp_env = std::getenv("RTMI_GRID_ASPECT");
-  const double asp = asp_env && std::atof(asp_env) > 0 ? std::atof(asp_env) : 1.0;
-  const double cell_a[3] = {cell * std::sqrt(asp), cell, cell / std::sqrt(asp)};
-  int64_t total = 1;
-  for (int a = 0; a < 3; ++a) {
-    out.desc.n[a] = int32_t(std::min<double>(128, std::max<double>(1, std::ceil(e[a] / cell_a[a]))));
-    total *= out.desc.n[a];
-  }
-  if (total > 16384) return false;
-  for (int a = 0; a < 3; ++a) {
-    // origin rounded down, cell size rounded up: the float cells cover the box
-    float g0 = float(lo[a]);
-    if (double(g0) > lo[a]) g0 = std::nextafter(g0, -INFINITY);
-    float h = float(e[a] / out.desc.n[a]);
-    while (double(g0) + double(h) * out.desc.n[a] < hi[a]) h = std::nextafter(h, INFINITY);
-    out.desc.g0[a] = g0;
-    out.desc.h[a] = h;
-    out.desc.inv_h[a] = 1.0f / h;
-    out.desc.g1[a] = std::fmaf(float(out.desc.n[a]), h, g0);
-  }
-  out.desc.ncells = int32_t(total);
-  if (!grid_strides(out.desc)) return false;  // (never at <= 128 cells per axis; the walk's 24-bit multiplies rest on it)
-  std::vector<std::vector<uint16_t>> lists(static_cast<size_t>(total));
-  for (int32_t k : small) {  // ascending scene index
-    const double *c = b.cr + 4 * k, R = std::fabs(c[3]) + b.margin(k);
-    int c0[3], c1[3];
-    for (int a = 0; a < 3; ++a) {
-      // cell c spans [g0 + c*h, g0 + (c+1)*h]: every cell the grown box touches
-      const double g0 = out.desc.g0[a], h = out.desc.h[a];
-      c0[a] = std::max(0, std::min(out.desc.n[a] - 1, int(std::floor((c[a] - R - g0) / h))));
-      c1[a] = std::max(0, std::min(out.desc.n[a] - 1, int(std::floor((c[a] + R - g0) / h))));
-    }
-    for (int z = c0[2]; z <= c1[2]; ++z)
-      for (int y = c0[1]; y <= c1[1]; ++y)
-        for (int x = c0[0]; x <= c1[0]; ++x)
-          lists[size_t(x + out.desc.n[0] * (y + out.desc.n[1] * z))].push_back(uint16_t(k));
-  }
-  // the LDS sphere array: the scene's spheres at their scene indices
-  out.sph.assign(b.g.begin(), b.g.begin() + n);
-  out.cells.resize(size_t(total) + 1);
-  for (int64_t cidx = 0; cidx < total; ++cidx) {
-    out.cells[size_t(cidx)] = uint32_t(out.refs.size());
-    for (uint16_t k : lists[size_t(cidx)]) out.refs.push_back(uint32_t(k) * 16u);
-  }
-  out.cells[size_t(total)] = uint32_t(out.refs.size());
-  out.desc.nrefs = int32_t(out.refs.size());
-  out.desc.cells_off = 16u * uint32_t(nbig_slots + out.desc.nrefs);  // grid_lds_bytes' layout
-  out.desc.idx_off = out.desc.cells_off + 4u * uint32_t(out.desc.ncells + 1);
-  // The grid is staged in LDS only while a 4-wave block (its grid copy, one
-  // accumulator set, the static LDS) still leaves 8 blocks per CU; a larger
-  // one is walked in global memory (Accel::grid_gmem).  Measured
-  // (tools/large_scene_bench.py, profiles/r05/large/): the final scene's
-  // 17.6 KB grid 1.05 ms in LDS vs 1.13 in global memory (config 2: 19.2 vs
-  // 20.2 ms); 1 604 spheres (a 58 KB grid, 2 blocks per CU) 2.71 vs 1.13 ms.
-  // RTMI_GRID_LDS_MAX overrides the byte limit (A/B).
-  // (the block's four tile lists, 2 kTileListCap bytes each, come out of the
-  // same budget)
-  const char *lim_env = std::getenv("RTMI_GRID_LDS_MAX");
-  const size_t lds_max = lim_env && std::atoll(lim_env) > 0
-                             ? size_t(std::atoll(lim_env))
-                             : 160 * 1024 / 8 - 3 * 64 * 8 - 256 - GridShape<true>::waves * 2 * kTileListCap;
-  out.fits_lds = grid_lds_bytes(nbig_slots, out.desc.ncells, out.desc.nrefs) <= lds_max;
-  // The tile lists' table: the sphere with the radius the grid's cells list it
-  // by (its own margin, 1e-3 of its coordinate scale: the same distance from
-  // float error), rounded up, and the first record slot that holds it.
-  std::vector<uint32_t> first(size_t(n), UINT32_MAX);
-  for (size_t p = out.refs.size(); p-- > 0;) first[out.refs[p] >> 4] = uint32_t(nbig_slots) + uint32_t(p);
-  if (size_t(nbig_slots) + out.refs.size() <= 65536) {
-    for (int32_t k : small) {
-      const double *c = b.cr + 4 * k, R = std::fabs(c[3]) + b.margin(k);
-      float rg = float(R);
-      if (double(rg) < R) rg = std::nextafter(rg, INFINITY);
-      out.tile_sph.push_back(make_float4(float(c[0]), float(c[1]), float(c[2]), rg));
-      out.tile_keys.push_back(first[size_t(k)]);
-    }
-    // The big slots by the same rule on the sphere's own scale: 1e-3 of its
-    // radius — 1 unit on the R = 1000 ground, where the cells' margin, which
-    // counts the centre's distance too, gives 2 and lifts the horizon over
-    // another 6 % of config 2's tiles — and 1e-5 of its centre's coordinates,
-    // 100 times their float spacing, which is what the centre's rounding and
-    // tile_may_hit's differences from it can be off by (on the ground 1e-4).
-    if (big.size() <= size_t(kTileBigMax))
-      for (int32_t k : big) {  // ascending scene index: slot order
-        const double *c = b.cr + 4 * k;
-        const double cmax = std::max(std::max(std::fabs(c[0]), std::fabs(c[1])), std::fabs(c[2]));
-        const double R = std::fabs(c[3]) + 1e-3 * (1.0 + std::fabs(c[3])) + 1e-5 * cmax + b.margin_scene;
-        float rg = float(R);
-        if (double(rg) < R) rg = std::nextafter(rg, INFINITY);
-        out.tile_big.push_back(make_float4(float(c[0]), float(c[1]), float(c[2]), rg));
-      }
-  }
-  return true;
-}
-
-// The rows and columns of tile `tile` of a strip (render_kernel's item
-// geometry): columns [x0, x0 + vw), image rows j_lo .. j_hi
-void tile_extent(int32_t W, int32_t row0, int32_t row_step, int32_t nvalid, int32_t tw, int32_t tile, int32_t &x0,
-                 int32_t &vw, int32_t &j_lo, int32_t &j_hi) {
-  const int32_t th = 64 / tw, tiles_x = (W + tw - 1) / tw, ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int32_t y0 = ty * th, vh = std::min(th, nvalid - y0);
-  x0 = tx * tw;
-  vw = std::min(tw, W - x0);
-  j_lo = row0 + y0 * row_step;
-  j_hi = row0 + (y0 + vh - 1) * row_step;
-}
 }  // namespace
 
 RTMI_EXPORT int rt_ctx_set_ordering(rt_ctx *ctx, int32_t ordering) {
@@ -1904,176 +1679,93 @@ RTMI_EXPORT int rt_ctx_accel_info(rt_ctx *ctx, int32_t *n_big, int32_t *n_nodes)
   return RT_OK;
 }
 
+// The host work is rtmi_accel_build.cpp's (build_accel: records, big / small
+// split, BVH, grid, tile table); here: whether each structure is staged in LDS
+// (a fact of the block shape, GridShape), the packed pairs, and the uploads.
 RTMI_EXPORT int rt_ctx_set_scene(rt_ctx *ctx, const rt_scene *scene) {
   if (!ctx || !scene || scene->n <= 0 || !scene->center_radius || !scene->mat_kind || !scene->mat_params)
     return set_error(RT_EINVAL, "rt_ctx_set_scene: bad argument");
   const int n = scene->n;
-  std::vector<float4> g(n + kGeomPad, make_float4(0.f, 0.f, 0.f, 0.f)), s0(n), s1(n);
-  std::vector<double4> g64(n), s064(n), s164(n);
-  for (int k = 0; k < n; k++) {
-    const double *c = scene->center_radius + 4 * k;
-    const double *m = scene->mat_params + 4 * k;
-    const int kind = scene->mat_kind[k];
-    if (kind < RT_MAT_LAMBERTIAN || kind > RT_MAT_DIELECTRIC)
-      return set_error(RT_EUNSUPPORTED, "object %d: unsupported material kind %d", k, kind);
-    const double fuzz = m[3] < 1 ? m[3] : 1;  // metal ctor material.h:39
-    const float r = float(c[3]), ir = float(m[3]);
-    // S = |c|^2 - r^2 of the float-rounded sphere, in double then rounded
-    // (the oracle computes the identical expression)
-    const float cx = float(c[0]), cy = float(c[1]), cz = float(c[2]);
-    const float S = float(double(cx) * cx + double(cy) * cy + double(cz) * cz - double(r) * r);
-    g[k] = make_float4(cx, cy, cz, S);
-    s0[k] = make_float4(1.0f / r, float(m[0]), float(m[1]), float(m[2]));
-    s1[k] = make_float4(float(kind), float(fuzz), ir, 1.0f / ir);
-    if (kind == RT_MAT_DIELECTRIC) {
-      // Schlick's r0 for both faces (material.h:91-96), in the float
-      // arithmetic the kernels would repeat per scatter: front (ratio 1/ir)
-      // in shade1.y, back (ratio ir) in shade0.y — fields a dielectric does
-      // not otherwise read (no albedo, no fuzz)
-      auto r0_of = [](float x) {
-        const float q = (1.0f - x) / (1.0f + x);
-        return q * q;
-      };
-      s1[k].y = r0_of(1.0f / ir);
-      s0[k].y = r0_of(ir);
-    }
-    g64[k] = make_double4(c[0], c[1], c[2], c[3] * c[3]);
-    s064[k] = make_double4(1 / c[3], m[0], m[1], m[2]);
-    s164[k] = make_double4(double(kind), fuzz, m[3], 1.0 / m[3]);
-  }
+  AccelBuild ab;
+  if (int rc = build_accel(scene, ab)) return rc;
   // sphere pairs for the packed loop: n padded to a multiple of 2*kPairGroup
-  // with never-hit dummies, plus kPairGroup pairs of prefetch padding
+  // with never-hit dummies; the big spheres' likewise, by slot
   const int n_pad = (n + 2 * kPairGroup - 1) / (2 * kPairGroup) * (2 * kPairGroup);
-  const int npairs = n_pad / 2;
-  std::vector<SpherePair> pr(npairs + kPairGroup);
-  for (auto &p : pr) {
-    p.cx = f2v{0.f, 0.f}; p.cy = f2v{0.f, 0.f}; p.cz = f2v{0.f, 0.f}; p.S = f2v{kDummyS, kDummyS};
-  }
-  for (int k = 0; k < n; k++) {
-    SpherePair &p = pr[k / 2];
-    const int h = k & 1;
-    p.cx[h] = g[k].x; p.cy[h] = g[k].y; p.cz[h] = g[k].z; p.S[h] = g[k].w;
-  }
+  const size_t nb_pad = ab.big_slots.size();
+  const std::vector<SpherePair> pr = pack_pairs(ab.g.data(), nullptr, size_t(n), size_t(n_pad));
+  const std::vector<SpherePair> bp = pack_pairs(ab.g.data(), ab.big_slots.data(), nb_pad, nb_pad);
+  std::vector<int32_t> bidx(nb_pad + 2 * kPairGroup, -1);  // (prefetch padding behind the slots)
+  std::copy(ab.big_slots.begin(), ab.big_slots.end(), bidx.begin());
   DeviceGuard guard(ctx->device);
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   int rc;
-  if ((rc = dev_alloc(&ctx->geom, n + kGeomPad)) || (rc = dev_alloc(&ctx->sh0, n)) || (rc = dev_alloc(&ctx->sh1, n)) ||
-      (rc = dev_alloc(&ctx->geom64, n)) || (rc = dev_alloc(&ctx->sh064, n)) || (rc = dev_alloc(&ctx->sh164, n)) ||
-      (rc = dev_alloc(&ctx->pairs, pr.size())))
+  Uploads up;
+  std::vector<char> image;  // (lives until copy_all)
+  if ((rc = up.upload(&ctx->pairs, pr)) || (rc = up.upload(&ctx->geom, ab.g)) || (rc = up.upload(&ctx->sh0, ab.s0)) ||
+      (rc = up.upload(&ctx->sh1, ab.s1)) || (rc = up.upload(&ctx->geom64, ab.g64)) ||
+      (rc = up.upload(&ctx->sh064, ab.s064)) || (rc = up.upload(&ctx->sh164, ab.s164)) ||
+      (rc = up.upload(&ctx->big_pairs, bp)) || (rc = up.upload(&ctx->big_idx, bidx)) ||
+      (rc = up.upload(&ctx->nodes, ab.nodes)) || (rc = up.upload(&ctx->bvh_sph, ab.bvh_sph)) ||
+      (rc = up.upload(&ctx->bvh_idx, ab.bvh_idx)))
     return rc;
-  HIP_TRY(hipMemcpy(ctx->pairs, pr.data(), pr.size() * sizeof(SpherePair), hipMemcpyHostToDevice));
-  ctx->npairs = npairs;
-  HIP_TRY(hipMemcpy(ctx->geom, g.data(), (n + kGeomPad) * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->sh0, s0.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->sh1, s1.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->geom64, g64.data(), n * sizeof(double4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->sh064, s064.data(), n * sizeof(double4), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->sh164, s164.data(), n * sizeof(double4), hipMemcpyHostToDevice));
-  // BVH: spheres much larger than the typical one (the ground) stay brute force
+  ctx->npairs = n_pad / 2;
+  ctx->nbig = ab.nbig;
+  ctx->nbig_pairs = int32_t(nb_pad / 2);
+  ctx->nbvh_sph = int32_t(ab.bvh_sph.size());
+  ctx->nnodes = int32_t(ab.nodes.size());
   {
-    std::vector<double> rad(n);
-    for (int k = 0; k < n; k++) rad[k] = std::fabs(scene->center_radius[4 * k + 3]);
-    std::vector<double> sorted_r = rad;
-    std::nth_element(sorted_r.begin(), sorted_r.begin() + n / 2, sorted_r.end());
-    const double med = sorted_r[n / 2];
-    std::vector<int32_t> big, small;
-    double scale = 0;  // the whole scene's, big spheres included
-    for (int k = 0; k < n; k++) {
-      (rad[k] > RTMI_BIG_FACTOR * med ? big : small).push_back(k);
-      for (int a = 0; a < 3; ++a) scale = std::max(scale, std::fabs(scene->center_radius[4 * k + a]) + rad[k]);
-    }
-    BvhBuilder b{scene->center_radius, g, 1e-6 * scale, {}, {}, {}};
-    if (!small.empty()) b.build(small.data(), int(small.size()));
-    const int nb_pad = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
-    std::vector<SpherePair> bp(nb_pad / 2 + kPairGroup);
-    std::vector<int32_t> bidx(size_t(nb_pad) + 2 * kPairGroup, -1);
-    for (auto &p : bp) {
-      p.cx = f2v{0.f, 0.f}; p.cy = f2v{0.f, 0.f}; p.cz = f2v{0.f, 0.f}; p.S = f2v{kDummyS, kDummyS};
-    }
-    for (size_t s = 0; s < big.size(); s++) {  // ascending scene index
-      SpherePair &p = bp[s / 2];
-      const int h = int(s & 1), k = big[s];
-      p.cx[h] = g[k].x; p.cy[h] = g[k].y; p.cz[h] = g[k].z; p.S[h] = g[k].w;
-      bidx[s] = k;
-    }
-    if ((rc = dev_alloc(&ctx->big_pairs, bp.size())) || (rc = dev_alloc(&ctx->big_idx, bidx.size())) ||
-        (rc = dev_alloc(&ctx->nodes, std::max<size_t>(b.nodes.size(), 1))) ||
-        (rc = dev_alloc(&ctx->bvh_sph, std::max<size_t>(b.sph.size(), 1))) ||
-        (rc = dev_alloc(&ctx->bvh_idx, std::max<size_t>(b.idx.size(), 1))))
-      return rc;
-    HIP_TRY(hipMemcpy(ctx->big_pairs, bp.data(), bp.size() * sizeof(SpherePair), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->big_idx, bidx.data(), bidx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!b.nodes.empty()) {
-      HIP_TRY(hipMemcpy(ctx->nodes, b.nodes.data(), b.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(ctx->bvh_sph, b.sph.data(), b.sph.size() * sizeof(float4), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(ctx->bvh_idx, b.idx.data(), b.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    ctx->nbig = int32_t(big.size());
-    ctx->nbig_pairs = nb_pad / 2;
-    ctx->nbvh_sph = int32_t(b.sph.size());
     // the BVH is staged in LDS while a block (BVH, one accumulator set, the
     // static LDS) still leaves 8 blocks per CU and its 16-bit scene indices
     // suffice; a larger one is walked in global memory (L2).  Measured
     // (profiles/r05/large/threshold_ab.txt): 488 spheres 1.90 ms in LDS vs
     // 2.06 global, 904 spheres 2.33 vs 2.34, 1 604 spheres 3.74 vs 2.42.
     // RTMI_BVH_LDS_MAX overrides the byte limit (A/B).
-    const size_t lds = bvh_lds_bytes(int32_t(b.nodes.size()), int32_t(b.sph.size()));
+    const size_t lds = bvh_lds_bytes(ctx->nnodes, ctx->nbvh_sph);
     const char *lim_env = std::getenv("RTMI_BVH_LDS_MAX");
     const size_t lds_max = lim_env && std::atoll(lim_env) > 0 ? std::min<size_t>(kBvhLdsMax, size_t(std::atoll(lim_env)))
                                                              : 160 * 1024 / 8 - 3 * 64 * 8 - 256;
-    ctx->nnodes = int32_t(b.nodes.size());
     ctx->bvh_global = ctx->force_bvh_global || !(lds <= lds_max && n <= 65535);
-    // uniform grid over the same small spheres
-    ctx->grid_ok = false;
-    GridBuild gb;
-    if (!small.empty() && build_grid(b, small, big, n, nb_pad, gb)) {
-      if ((rc = dev_alloc(&ctx->grid_sph, gb.sph.size())) || (rc = dev_alloc(&ctx->grid_cells, gb.cells.size())) ||
-          (rc = dev_alloc(&ctx->grid_refs, std::max<size_t>(gb.refs.size(), 1))))
-        return rc;
-      HIP_TRY(hipMemcpy(ctx->grid_sph, gb.sph.data(), gb.sph.size() * sizeof(float4), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(ctx->grid_cells, gb.cells.data(), gb.cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      if (!gb.refs.empty())
-        HIP_TRY(hipMemcpy(ctx->grid_refs, gb.refs.data(), gb.refs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      ctx->grid = gb.desc;
-      ctx->grid.cells = ctx->grid_cells;
-      ctx->grid.refs = ctx->grid_refs;
-      ctx->ngrid_sph = int32_t(gb.sph.size());
-      ctx->grid_global = ctx->force_grid_global || !gb.fits_lds;
-      ctx->ntile = ctx->ntile_big = 0;
-      if (!ctx->grid_global && !gb.tile_sph.empty()) {
-        // {centre, grown radius} per small sphere, then the slot keys, then
-        // {centre, grown radius} per big slot
-        const size_t ns = gb.tile_sph.size(), nk = (ns + 3) / 4, nb = ctx->tile_big ? gb.tile_big.size() : 0;
-        std::vector<float4> tab(ns + nk + nb);
-        std::copy(gb.tile_sph.begin(), gb.tile_sph.end(), tab.begin());
-        std::memcpy(tab.data() + ns, gb.tile_keys.data(), ns * sizeof(uint32_t));
-        std::copy(gb.tile_big.begin(), gb.tile_big.begin() + nb, tab.begin() + ns + nk);
-        ctx->ntile_big = int32_t(nb);
-        if ((rc = dev_alloc(&ctx->tile_sph, tab.size()))) return rc;
-        HIP_TRY(hipMemcpy(ctx->tile_sph, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        ctx->ntile = int32_t(ns);
-      }
-      if (ctx->grid_global) {
-        // the image stage_grid builds in LDS, offsets from 0: the slots (big
-        // spheres, then every cell's references as copies of their spheres'
-        // records), the cell starts, the slots' scene indices
-        const int32_t nbs = nb_pad, nrec = nbs + gb.desc.nrefs;
-        std::vector<char> img(grid_lds_bytes(nbs, gb.desc.ncells, gb.desc.nrefs), 0);
-        float4 *rec = reinterpret_cast<float4 *>(img.data());
-        uint32_t *cst = reinterpret_cast<uint32_t *>(img.data() + gb.desc.cells_off);
-        uint16_t *ix = reinterpret_cast<uint16_t *>(img.data() + gb.desc.idx_off);
-        for (int32_t i = 0; i < nrec; ++i) {
-          const int32_t k = i < nbs ? bidx[size_t(i)] : int32_t(gb.refs[size_t(i - nbs)] >> 4);  // dummies: -1
-          rec[i] = k < 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : gb.sph[size_t(k)];
-          ix[i] = uint16_t(k < 0 ? 0 : k);
-        }
-        for (int32_t i = 0; i <= gb.desc.ncells; ++i) cst[i] = 16u * (uint32_t(nbs) + gb.cells[size_t(i)]);
-        if ((rc = dev_alloc(&ctx->grid_gmem, img.size()))) return rc;
-        HIP_TRY(hipMemcpy(ctx->grid_gmem, img.data(), img.size(), hipMemcpyHostToDevice));
-      }
-      ctx->grid_ok = true;
-    }
   }
+  // uniform grid over the same small spheres
+  ctx->grid_ok = false;
+  if (ab.has_grid) {
+    // The grid is staged in LDS only while a 4-wave block (its grid copy, one
+    // accumulator set, the static LDS) still leaves 8 blocks per CU; a larger
+    // one is walked in global memory (Accel::grid_gmem).  Measured
+    // (tools/large_scene_bench.py, profiles/r05/large/): the final scene's
+    // 17.6 KB grid 1.05 ms in LDS vs 1.13 in global memory (config 2: 19.2 vs
+    // 20.2 ms); 1 604 spheres (a 58 KB grid, 2 blocks per CU) 2.71 vs 1.13 ms.
+    // RTMI_GRID_LDS_MAX overrides the byte limit (A/B).
+    // (the block's four tile lists, 2 kTileListCap bytes each, come out of the
+    // same budget)
+    const char *lim_env = std::getenv("RTMI_GRID_LDS_MAX");
+    const size_t lds_max = lim_env && std::atoll(lim_env) > 0
+                               ? size_t(std::atoll(lim_env))
+                               : 160 * 1024 / 8 - 3 * 64 * 8 - 256 - GridShape<true>::waves * 2 * kTileListCap;
+    const bool fits_lds = grid_lds_bytes(int32_t(nb_pad), ab.grid.ncells, ab.grid.nrefs) <= lds_max;
+    if ((rc = up.upload(&ctx->grid_sph, ab.g, size_t(n))) || (rc = up.upload(&ctx->grid_cells, ab.cells)) ||
+        (rc = up.upload(&ctx->grid_refs, ab.refs)))
+      return rc;
+    ctx->grid = ab.grid;
+    ctx->grid.cells = ctx->grid_cells;
+    ctx->grid.refs = ctx->grid_refs;
+    ctx->ngrid_sph = n;
+    ctx->grid_global = ctx->force_grid_global || !fits_lds;
+    ctx->ntile = ctx->ntile_big = 0;
+    if (!ctx->grid_global && ab.ntile > 0) {
+      // the table up to the big slots' part, which RTMI_TILE_BIG=0 leaves out
+      const size_t ns = size_t(ab.ntile), nb = ctx->tile_big ? size_t(ab.ntile_big) : 0;
+      if ((rc = up.upload(&ctx->tile_sph, ab.tile_tab, ns + (ns + 3) / 4 + nb))) return rc;
+      ctx->ntile = int32_t(ns);
+      ctx->ntile_big = int32_t(nb);
+    }
+    if (ctx->grid_global) {
+      image = grid_image(ab);
+      if ((rc = up.upload(&ctx->grid_gmem, image))) return rc;
+    }
+    ctx->grid_ok = true;
+  }
+  if ((rc = up.copy_all())) return rc;
   ctx->n = n;
   return RT_OK;
 }
@@ -2084,62 +1776,6 @@ RTMI_EXPORT int rt_ctx_grid_info(rt_ctx *ctx, int32_t *dims3, int32_t *n_refs, i
   if (dims3) for (int a = 0; a < 3; ++a) dims3[a] = ctx->grid.n[a];
   if (n_refs) *n_refs = ctx->grid.nrefs;
   if (lds_bytes) *lds_bytes = int32_t(grid_lds_bytes(2 * ctx->nbig_pairs, ctx->grid.ncells, ctx->grid.nrefs));
-  return RT_OK;
-}
-
-// Validation entry points (host only, no device): the cell-start strides
-// grid_strides gives a grid of n3 cells per axis, or RT_EINVAL where it
-// refuses the grid; and the cell counts and strides of the descriptor
-// build_grid fills for a scene (the split into big and small spheres as in
-// rt_ctx_set_scene), with its origin and cell size (box6, optional).
-RTMI_EXPORT int rt_debug_grid_strides(const int32_t *n3, uint32_t *strides2) {
-  if (!n3 || !strides2) return set_error(RT_EINVAL, "rt_debug_grid_strides: bad argument");
-  GridDesc d{};
-  for (int a = 0; a < 3; ++a) d.n[a] = n3[a];
-  if (!grid_strides(d)) return set_error(RT_EINVAL, "grid of %d x %d x %d cells: over the walk's 24-bit bound", n3[0], n3[1], n3[2]);
-  strides2[0] = d.row_bytes;
-  strides2[1] = d.layer_bytes;
-  return RT_OK;
-}
-
-namespace {
-// The grid rt_ctx_set_scene builds for a scene, on the host alone (false: the
-// scene has none); nbs: the big spheres' record slots before the cells'
-bool host_grid(const rt_scene *scene, GridBuild &gb, int32_t &nbs, std::vector<int32_t> *big_out = nullptr) {
-  const int n = scene->n;
-  std::vector<float4> g(n, make_float4(0.f, 0.f, 0.f, 0.f));  // (build_grid copies the records; their values do not shape the grid)
-  std::vector<double> rad(n);
-  for (int k = 0; k < n; k++) rad[k] = std::fabs(scene->center_radius[4 * k + 3]);
-  std::vector<double> sorted_r = rad;
-  std::nth_element(sorted_r.begin(), sorted_r.begin() + n / 2, sorted_r.end());
-  const double med = sorted_r[n / 2];
-  std::vector<int32_t> big, small;
-  double scale = 0;
-  for (int k = 0; k < n; k++) {
-    (rad[k] > RTMI_BIG_FACTOR * med ? big : small).push_back(k);
-    for (int a = 0; a < 3; ++a) scale = std::max(scale, std::fabs(scene->center_radius[4 * k + a]) + rad[k]);
-  }
-  BvhBuilder b{scene->center_radius, g, 1e-6 * scale, {}, {}, {}};
-  nbs = big.empty() ? 0 : (int(big.size()) + 2 * kBigGroup - 1) / (2 * kBigGroup) * (2 * kBigGroup);
-  if (big_out) *big_out = big;  // the big slots' scene indices
-  return !small.empty() && build_grid(b, small, big, n, nbs, gb);
-}
-}  // namespace
-
-RTMI_EXPORT int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint32_t *strides2, float *box6) {
-  if (!scene || scene->n <= 0 || !scene->center_radius || !dims3 || !strides2)
-    return set_error(RT_EINVAL, "rt_debug_grid_layout: bad argument");
-  GridBuild gb;
-  int32_t nb_pad;
-  if (!host_grid(scene, gb, nb_pad)) return set_error(RT_EUNSUPPORTED, "no grid for this scene");
-  for (int a = 0; a < 3; ++a) dims3[a] = gb.desc.n[a];
-  strides2[0] = gb.desc.row_bytes;
-  strides2[1] = gb.desc.layer_bytes;
-  if (box6)  // the grid's origin and cell size, as the walk reads them
-    for (int a = 0; a < 3; ++a) {
-      box6[a] = gb.desc.g0[a];
-      box6[3 + a] = gb.desc.h[a];
-    }
   return RT_OK;
 }
 
@@ -2168,95 +1804,6 @@ RTMI_EXPORT int rt_ctx_set_kernel(rt_ctx *ctx, int32_t kind) {
   return RT_OK;
 }
 
-// Automatic tile shape: 8x8 unless 16x4 leaves fewer idle lanes in partial
-// tiles.  A 100-row strip (1/8 of config 2's rows) fills 25 rows of 16x4 tiles
-// but 12.5 of 8x8: 7.04 vs 7.16 ms, while the whole frame runs 50.6 ms with 8x8
-// and 50.9 with 16x4 (profiles/r01/session6/tile_ab.txt).
-static int auto_tile_w(int32_t W, int32_t rows) {
-  auto idle = [&](int64_t tw) {
-    const int64_t th = 64 / tw;
-    return ((W + tw - 1) / tw) * tw * ((rows + th - 1) / th) * th - int64_t(W) * rows;
-  };
-  return idle(16) < idle(8) ? 16 : 8;
-}
-
-// Validation entry point (host only, no device): the tile lists render_kernel
-// builds, by the same tile_bundle / tile_may_hit, for the
-// strip of rows row0 + r row_step, r < nrows, of a W x H image in tiles of
-// tile_w x 64 / tile_w (0: the automatic shape).  tile >= 0: that tile's list
-// as scene indices in out_indices[cap] and its length in out_count[0]; tile
-// -1: every tile's, cap entries and one count each.  A count of -1: more than
-// cap spheres pass, the tile has no list (its batches walk the grid).
-RTMI_EXPORT int rt_debug_tile_list(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
-                                   int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t cap,
-                                   int32_t *out_indices, int32_t *out_count) {
-  if (!scene || scene->n <= 0 || !scene->center_radius || !camera || !out_indices || !out_count)
-    return set_error(RT_EINVAL, "rt_debug_tile_list: bad argument");
-  if (W < 2 || H < 2 || row0 < 0 || row0 >= H || row_step < 1 || nrows < 1 || cap < 1 || cap > kTileListCap ||
-      (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64))
-    return set_error(RT_EINVAL, "rt_debug_tile_list: bad image, strip, tile shape or cap");
-  const int32_t nvalid = int32_t(std::min<int64_t>(nrows, (int64_t(H) - row0 + row_step - 1) / row_step));
-  const int32_t tw = tile_w ? tile_w : auto_tile_w(W, nvalid), th = 64 / tw;
-  const int64_t tiles = int64_t((W + tw - 1) / tw) * ((nvalid + th - 1) / th);
-  if (tile < -1 || tile >= tiles) return set_error(RT_EINVAL, "rt_debug_tile_list: tile %d of %lld", tile, (long long)tiles);
-  GridBuild gb;
-  int32_t nbs;
-  if (!host_grid(scene, gb, nbs) || gb.tile_sph.empty()) return set_error(RT_EUNSUPPORTED, "no tile lists for this scene");
-  const Cam<float> cam = cam_f(camera);
-  for (int64_t t = tile < 0 ? 0 : tile, o = 0; t < (tile < 0 ? tiles : tile + 1); ++t, ++o) {
-    int32_t x0, vw, j_lo, j_hi, cnt = 0;
-    tile_extent(W, row0, row_step, nvalid, tw, int32_t(t), x0, vw, j_lo, j_hi);
-    const TileBundle tb = tile_bundle(cam, W, H, x0, vw, j_lo, j_hi);
-    for (size_t i = 0; i < gb.tile_sph.size(); ++i) {
-      const float4 s = gb.tile_sph[i];
-      if (!tile_may_hit(tb, s.x, s.y, s.z, s.w)) continue;
-      // the key names a record slot; the slot's reference names the sphere
-      if (cnt < cap) out_indices[o * cap + cnt] = int32_t(gb.refs[gb.tile_keys[i] - uint32_t(nbs)] >> 4);
-      ++cnt;
-    }
-    out_count[o] = cnt <= cap ? cnt : -1;
-  }
-  return RT_OK;
-}
-
-// The same for the big spheres (the same host code; rt_debug_tile_list stays
-// the small spheres alone): the big spheres the kernel appends to the tile's
-// list, as scene indices in out_indices[kTileBigMax] per tile and their number
-// in out_count.  A count of -1 for every tile: the scene has more than
-// kTileBigMax big spheres and its lists name none (every batch runs hit_big).
-// (The kernel appends them where the tile has a list and the list's 32
-// entries hold both; RTMI_TILE_BIG is not read here.)
-RTMI_EXPORT int rt_debug_tile_big(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
-                                  int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t *out_indices,
-                                  int32_t *out_count) {
-  if (!scene || scene->n <= 0 || !scene->center_radius || !camera || !out_indices || !out_count)
-    return set_error(RT_EINVAL, "rt_debug_tile_big: bad argument");
-  if (W < 2 || H < 2 || row0 < 0 || row0 >= H || row_step < 1 || nrows < 1 ||
-      (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64))
-    return set_error(RT_EINVAL, "rt_debug_tile_big: bad image, strip or tile shape");
-  const int32_t nvalid = int32_t(std::min<int64_t>(nrows, (int64_t(H) - row0 + row_step - 1) / row_step));
-  const int32_t tw = tile_w ? tile_w : auto_tile_w(W, nvalid), th = 64 / tw;
-  const int64_t tiles = int64_t((W + tw - 1) / tw) * ((nvalid + th - 1) / th);
-  if (tile < -1 || tile >= tiles) return set_error(RT_EINVAL, "rt_debug_tile_big: tile %d of %lld", tile, (long long)tiles);
-  GridBuild gb;
-  int32_t nbs;
-  std::vector<int32_t> big;
-  if (!host_grid(scene, gb, nbs, &big) || gb.tile_sph.empty()) return set_error(RT_EUNSUPPORTED, "no tile lists for this scene");
-  const bool none = big.size() > size_t(kTileBigMax);
-  const Cam<float> cam = cam_f(camera);
-  for (int64_t t = tile < 0 ? 0 : tile, o = 0; t < (tile < 0 ? tiles : tile + 1); ++t, ++o) {
-    int32_t x0, vw, j_lo, j_hi, cnt = 0;
-    tile_extent(W, row0, row_step, nvalid, tw, int32_t(t), x0, vw, j_lo, j_hi);
-    const TileBundle tb = tile_bundle(cam, W, H, x0, vw, j_lo, j_hi);
-    for (size_t i = 0; i < gb.tile_big.size(); ++i) {
-      const float4 s = gb.tile_big[i];
-      if (tile_may_hit(tb, s.x, s.y, s.z, s.w)) out_indices[o * kTileBigMax + cnt++] = big[i];
-    }
-    out_count[o] = none ? -1 : cnt;
-  }
-  return RT_OK;
-}
-
 RTMI_EXPORT int rt_ctx_set_tuning(rt_ctx *ctx, int32_t tile_w, int32_t chunk) {
   if (!ctx) return set_error(RT_EINVAL, "null ctx");
   if (tile_w != 0 && tile_w != 8 && tile_w != 16 && tile_w != 32 && tile_w != 64)
@@ -2274,6 +1821,15 @@ size_t accel_lds_bytes(const Accel &acc, int kind) {
   if (kind >= 4) return 0;  // (the grid in global memory)
   if (kind >= 2) return grid_lds_bytes(2 * acc.nbig_pairs, acc.grid.ncells, acc.grid.nrefs);
   return 0;
+}
+
+// The closest-hit search of the context's setting and scene: 0 brute force,
+// 1 the BVH, 2 the grid, 3 the grid walked as one y layer (hit_world_grid<..,
+// true>), +2 for a grid walked in global memory.  A grid setting without a
+// grid (a scene it does not fit, e.g. thousands of spheres) leaves the BVH.
+int acc_kind_of(const rt_ctx *ctx) {
+  return ctx->accel == RT_ACCEL_GRID && ctx->grid_ok ? (ctx->grid.n[1] == 1 ? 3 : 2) + (ctx->grid_global ? 2 : 0)
+                                                     : (ctx->accel != RT_ACCEL_NONE && ctx->nnodes > 0 ? 1 : 0);
 }
 
 // The Accel view of the context's structure of `kind` (1 BVH, 2 grid, 3 the
@@ -2431,9 +1987,7 @@ int render_rows_impl(rt_ctx *ctx, const rt_camera *cam, int32_t W, int32_t H, in
   // the y stepping dropped, hit_world_grid<.., true>: the same cells, 3% faster
   // on config 2)
   // (a grid that does not fit, e.g. thousands of spheres, leaves the BVH)
-  const int acc_kind = ctx->accel == RT_ACCEL_GRID && ctx->grid_ok
-                           ? (ctx->grid.n[1] == 1 ? 3 : 2) + (ctx->grid_global ? 2 : 0)
-                           : (ctx->accel != RT_ACCEL_NONE && ctx->nnodes > 0 ? 1 : 0);
+  const int acc_kind = acc_kind_of(ctx);
   const bool bvh = acc_kind != 0;
   // the resident grid kernel: accelerated scenes, when
   // selected, in the experimental build only (measured slower than the grid
@@ -2761,19 +2315,14 @@ struct CkptHeader {
 };
 static_assert(sizeof(CkptHeader) == 64, "checkpoint header layout");
 
-uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
-  const unsigned char *b = static_cast<const unsigned char *>(p);
-  for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-  return h;
-}
 uint64_t scene_hash(const rt_scene *s) {
-  uint64_t h = 14695981039346656037ull;
+  uint64_t h = kFnvBasis;
   h = fnv1a(h, &s->n, sizeof s->n);
   h = fnv1a(h, s->center_radius, sizeof(double) * 4 * size_t(s->n));
   h = fnv1a(h, s->mat_kind, sizeof(int32_t) * size_t(s->n));
   return fnv1a(h, s->mat_params, sizeof(double) * 4 * size_t(s->n));
 }
-uint64_t camera_hash(const rt_camera *c) { return fnv1a(14695981039346656037ull, c, sizeof *c); }
+uint64_t camera_hash(const rt_camera *c) { return fnv1a(kFnvBasis, c, sizeof *c); }
 }  // namespace
 
 RTMI_EXPORT int rt_accum_save(rt_ctx *ctx, const char *path, const rt_scene *scene, const rt_camera *cam, int32_t H,
@@ -2964,12 +2513,9 @@ RTMI_EXPORT int rt_ctx_debug_hits(rt_ctx *ctx, const float *rays, int32_t n, int
       (rc = dev_alloc(&d_t, size_t(n) * 2)))
     return rc;
   HIP_TRY(hipMemcpy(d_rays, rays, size_t(n) * 6 * sizeof(float), hipMemcpyHostToDevice));
-  // the walk the renders use, by render_rows_impl's rule (3: the one-layer
-  // grid walk; +2: walked in global memory; 1: the BVH, also where the grid
+  // the walk the renders use (acc_kind_of; the BVH also where the grid
   // setting has no grid, e.g. over 65 535 spheres)
-  const int kind = ctx->accel == RT_ACCEL_GRID && ctx->grid_ok
-                       ? (ctx->grid.n[1] == 1 ? 3 : 2) + (ctx->grid_global ? 2 : 0)
-                       : (ctx->accel != RT_ACCEL_NONE && ctx->nnodes > 0 ? 1 : 0);
+  const int kind = acc_kind_of(ctx);
   if (kind == 0) {
     (void)hipFree(d_rays); (void)hipFree(d_idx); (void)hipFree(d_t);
     return set_error(RT_EUNSUPPORTED, "rt_ctx_debug_hits: brute force only for this scene and setting (no structure)");

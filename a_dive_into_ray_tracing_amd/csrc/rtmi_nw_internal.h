@@ -12,7 +12,7 @@ namespace rtmi {
 namespace nw {
 
 // BVH node over objects: DFS order with skip links (the RTIOW BVH's format,
-// rtmi_path.h BvhNode): leaf = first << 4 | count, -1 for inner nodes.
+// rtmi_accel.h BvhNode): leaf = first << 4 | count, -1 for inner nodes.
 struct Node {
   float bmin[3];
   int32_t skip;

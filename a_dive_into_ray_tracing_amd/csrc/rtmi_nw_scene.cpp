@@ -696,7 +696,7 @@ struct ObjBvh {
 };
 
 // Uniform grid over the non-media objects, the RTIOW grid's
-// build (rtmi_device.hip build_grid) for general objects: an object whose box
+// build (rtmi_accel_build.cpp build_grid) for general objects: an object whose box
 // is more than 8x the median's largest extent (the R = 1000 ground, a
 // room-sized light) is tested brute force beside the grid; the others are
 // listed in every cell their margin-grown box overlaps.  Cell boundaries are

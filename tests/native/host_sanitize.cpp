@@ -2,9 +2,12 @@
 // UndefinedBehaviorSanitizer (built by `make -C a_dive_into_ray_tracing_amd/csrc
 // asan`; run by tests/test_sanitize.py, CPU only).  Covers the scene
 // generator, scene text files (valid and malformed), camera, PPM (P3/P6), PFM,
-// quantisation, the Next-Week scene builder, presets and flattening, and the
-// error paths of each.  No GPU call is made.  Exit 0 = every check passed and
-// the sanitizers reported nothing (they abort on the first report).
+// quantisation, the builders of the acceleration structures (BVH, grid, tile
+// tables, the grid's global-memory image: rtmi_accel_build.cpp, through its
+// rt_debug_* entry points), the Next-Week scene builder, presets and
+// flattening, and the error paths of each.  No GPU call is made.  Exit 0 =
+// every check passed and the sanitizers reported nothing (they abort on the
+// first report).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +31,66 @@ static void write_file(const std::string &p, const char *text) {
   FILE *f = std::fopen(p.c_str(), "wb");
   std::fputs(text, f);
   std::fclose(f);
+}
+
+// the validation entry points of rtmi_accel_build.cpp (exported, not in rtmi.h)
+extern "C" {
+int rt_debug_grid_strides(const int32_t *n3, uint32_t *strides2);
+int rt_debug_grid_layout(const rt_scene *scene, int32_t *dims3, uint32_t *strides2, float *box6);
+int rt_debug_tile_list(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
+                       int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t cap, int32_t *out_indices,
+                       int32_t *out_count);
+int rt_debug_tile_big(const rt_scene *scene, const rt_camera *camera, int32_t W, int32_t H, int32_t row0,
+                      int32_t row_step, int32_t nrows, int32_t tile_w, int32_t tile, int32_t *out_indices,
+                      int32_t *out_count);
+int rt_debug_accel_digest(const rt_scene *scene, uint64_t *out8);
+}
+
+// n lambertian spheres, sphere i's {centre, radius} written by fill(i, c); the
+// arrays live until the next call
+template <class Fill> static rt_scene plain_scene(int32_t n, Fill fill) {
+  static std::vector<double> cr, mp;
+  static std::vector<int32_t> kd;
+  cr.assign(4 * size_t(n), 0.0);
+  mp.assign(4 * size_t(n), 0.5);
+  kd.assign(size_t(n), RT_MAT_LAMBERTIAN);
+  for (int32_t i = 0; i < n; ++i) fill(i, cr.data() + 4 * size_t(i));
+  return rt_scene{n, cr.data(), kd.data(), mp.data()};
+}
+
+// Every builder entry point on one scene: the digest (all of build_accel and
+// the grid image), the grid layout, and the tile lists of every tile shape on a
+// strided strip (rows 3, 7, .. of 48 x 32) and of one tile of the whole image.
+// grid: the scene has a grid (else the three grid entry points refuse it);
+// many_big: more than kTileBigMax big spheres, every big count is -1.
+static void accel_checks(const rt_scene &sc, const rt_camera &cam, bool grid, bool many_big) {
+  uint64_t dg[8] = {0};
+  CHECK(rt_debug_accel_digest(&sc, dg) == 0 && dg[1] != 0);
+  int32_t dims[3] = {0, 0, 0};
+  uint32_t st[2] = {0, 0};
+  float box[6];
+  CHECK((rt_debug_grid_layout(&sc, dims, st, box) == 0) == grid);
+  if (grid) CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && st[0] == 4u * dims[0] && st[1] == st[0] * dims[1]);
+  const int caps[] = {32, 5};
+  for (int tw : {0, 8, 16, 32, 64})
+    for (int cap : caps) {
+      const int W = 48, H = 32, tiles = 8;  // at most 8 tiles: 8 strip rows of 48 pixels
+      std::vector<int32_t> idx(size_t(tiles) * 32, -7), cnt(tiles, -7), bidx(size_t(tiles) * 8, -7), bcnt(tiles, -7);
+      CHECK((rt_debug_tile_list(&sc, &cam, W, H, 3, 4, H, tw, -1, cap, idx.data(), cnt.data()) == 0) == grid);
+      CHECK((rt_debug_tile_big(&sc, &cam, W, H, 3, 4, H, tw, -1, bidx.data(), bcnt.data()) == 0) == grid);
+      if (!grid) continue;
+      const int ntiles = tw == 32 || tw == 64 ? 8 : 6;
+      for (int t = 0; t < ntiles; ++t) {
+        CHECK(cnt[t] >= -1 && cnt[t] <= cap);
+        for (int i = 0; i < cnt[t]; ++i) CHECK(idx[size_t(t) * cap + i] >= 0 && idx[size_t(t) * cap + i] < sc.n);
+        CHECK(many_big ? bcnt[t] == -1 : bcnt[t] >= 0 && bcnt[t] <= 8);
+        for (int i = 0; i < bcnt[t]; ++i) CHECK(bidx[size_t(t) * 8 + i] >= 0 && bidx[size_t(t) * 8 + i] < sc.n);
+      }
+      for (int t = ntiles; t < tiles; ++t) CHECK(cnt[t] == -7 && bcnt[t] == -7);  // nothing written past the strip's tiles
+    }
+  int32_t one[32], c1 = -7;
+  CHECK((rt_debug_tile_list(&sc, &cam, 48, 32, 0, 1, 32, 0, 5, 32, one, &c1) == 0) == grid);
+  CHECK((rt_debug_tile_big(&sc, &cam, 48, 32, 0, 1, 32, 0, 5, one, &c1) == 0) == grid);
 }
 
 int main(int argc, char **argv) {
@@ -143,6 +206,69 @@ int main(int argc, char **argv) {
     rt_nw_flat f;
     CHECK(rt_nw_scene_flat(s, &f) == 0 && f.n_obj == 1);
     CHECK(rt_nw_scene_destroy(s) == 0);
+  }
+  // --- builders of the acceleration structures (rtmi_accel_build.cpp) ---------
+  {
+    CHECK(rt_scene_random(1, g.data(), k.data(), m.data(), 600, &n) == 0);
+    accel_checks(rt_scene{n, g.data(), k.data(), m.data()}, cam, true, false);
+    CHECK(rt_scene_learn(g.data(), k.data(), m.data(), 600, &nl) == 0);
+    accel_checks(rt_scene{nl, g.data(), k.data(), m.data()}, cam, true, false);
+    // one sphere; 64 spheres with one centre and radius (zero-extent boxes, the
+    // 1e-6 floor of the grid's extent)
+    accel_checks(plain_scene(1, [](int, double *c) { c[0] = 1; c[1] = 2; c[2] = 3; c[3] = 0.5; }), cam, true, false);
+    accel_checks(plain_scene(64, [](int, double *c) { c[0] = c[1] = c[2] = 0.25; c[3] = 0.5; }), cam, true, false);
+    // 100 small spheres and 9 big ones: more than kTileBigMax, no big table
+    accel_checks(plain_scene(109, [](int i, double *c) {
+      const bool big = i % 12 == 0;  // 0, 12, .. 96: nine of them
+      c[0] = big ? 3.0 * i - 140 : 0.7 * (i % 10) - 3;
+      c[1] = big ? 10 : 0.1;
+      c[2] = big ? 40 - i : 0.7 * (i / 10) - 3;
+      c[3] = big ? 10 : 0.1;
+    }), cam, true, true);
+    // 70 000 spheres: over the grid's 65 535 (16-bit references), the BVH alone
+    accel_checks(plain_scene(70000, [](int i, double *c) {
+      c[0] = 0.5 * (i % 300); c[1] = 0.2 * ((i * 7) % 11); c[2] = 0.5 * (i / 300); c[3] = 0.2;
+    }), cam, false, false);
+    // refused arguments
+    CHECK(rt_scene_random(1, g.data(), k.data(), m.data(), 600, &n) == 0);
+    rt_scene fin{n, g.data(), k.data(), m.data()};
+    int32_t n3[3] = {20, 1, 20}, dims[3], idx[32 * 8], cnt[8];
+    uint32_t st[2];
+    uint64_t dg[8];
+    CHECK(rt_debug_grid_strides(n3, st) == 0 && st[0] == 80 && st[1] == 80);
+    CHECK(rt_debug_grid_strides(nullptr, st) != 0 && rt_debug_grid_strides(n3, nullptr) != 0);
+    n3[1] = 65536;
+    CHECK(rt_debug_grid_strides(n3, st) != 0);
+    n3[0] = 4096; n3[1] = 1024;
+    CHECK(rt_debug_grid_strides(n3, st) != 0);
+    rt_scene none = fin, empty = fin;
+    none.center_radius = nullptr;
+    empty.n = 0;
+    CHECK(rt_debug_grid_layout(nullptr, dims, st, nullptr) != 0 && rt_debug_grid_layout(&none, dims, st, nullptr) != 0);
+    CHECK(rt_debug_grid_layout(&empty, dims, st, nullptr) != 0 && rt_debug_grid_layout(&fin, nullptr, st, nullptr) != 0);
+    CHECK(rt_debug_grid_layout(&fin, dims, nullptr, nullptr) != 0);
+    CHECK(rt_debug_accel_digest(nullptr, dg) != 0 && rt_debug_accel_digest(&fin, nullptr) != 0);
+    CHECK(rt_debug_accel_digest(&none, dg) != 0 && rt_debug_accel_digest(&empty, dg) != 0);
+    k[3] = 7;  // an unknown material kind
+    CHECK(rt_debug_accel_digest(&fin, dg) != 0);
+    k[3] = 0;
+    auto list = [&](const rt_scene *s, const rt_camera *c, int W, int H, int row0, int step, int rows, int tw, int tile,
+                    int cap) { return rt_debug_tile_list(s, c, W, H, row0, step, rows, tw, tile, cap, idx, cnt); };
+    auto big = [&](const rt_scene *s, const rt_camera *c, int W, int H, int row0, int step, int rows, int tw, int tile) {
+      return rt_debug_tile_big(s, c, W, H, row0, step, rows, tw, tile, idx, cnt);
+    };
+    CHECK(list(&fin, &cam, 16, 8, 0, 1, 8, 0, 0, 32) == 0 && big(&fin, &cam, 16, 8, 0, 1, 8, 0, 0) == 0);
+    CHECK(list(nullptr, &cam, 16, 8, 0, 1, 8, 0, 0, 32) != 0 && big(nullptr, &cam, 16, 8, 0, 1, 8, 0, 0) != 0);
+    CHECK(list(&fin, nullptr, 16, 8, 0, 1, 8, 0, 0, 32) != 0 && big(&fin, nullptr, 16, 8, 0, 1, 8, 0, 0) != 0);
+    CHECK(list(&none, &cam, 16, 8, 0, 1, 8, 0, 0, 32) != 0 && big(&empty, &cam, 16, 8, 0, 1, 8, 0, 0) != 0);
+    CHECK(rt_debug_tile_list(&fin, &cam, 16, 8, 0, 1, 8, 0, 0, 32, nullptr, cnt) != 0);
+    CHECK(rt_debug_tile_big(&fin, &cam, 16, 8, 0, 1, 8, 0, 0, idx, nullptr) != 0);
+    CHECK(list(&fin, &cam, 1, 8, 0, 1, 8, 0, 0, 32) != 0 && big(&fin, &cam, 16, 1, 0, 1, 8, 0, 0) != 0);    // image
+    CHECK(list(&fin, &cam, 16, 8, -1, 1, 8, 0, 0, 32) != 0 && big(&fin, &cam, 16, 8, 8, 1, 8, 0, 0) != 0);   // row0
+    CHECK(list(&fin, &cam, 16, 8, 0, 0, 8, 0, 0, 32) != 0 && big(&fin, &cam, 16, 8, 0, 1, 0, 0, 0) != 0);    // step, rows
+    CHECK(list(&fin, &cam, 16, 8, 0, 1, 8, 12, 0, 32) != 0 && big(&fin, &cam, 16, 8, 0, 1, 8, 128, 0) != 0); // tile shape
+    CHECK(list(&fin, &cam, 16, 8, 0, 1, 8, 0, 0, 0) != 0 && list(&fin, &cam, 16, 8, 0, 1, 8, 0, 0, 33) != 0); // cap
+    CHECK(list(&fin, &cam, 16, 8, 0, 1, 8, 0, -2, 32) != 0 && big(&fin, &cam, 16, 8, 0, 1, 8, 0, 2) != 0);   // tile
   }
   std::vector<float> u(3000);
   CHECK(rt_nw_xorwow_uniforms(1984, 3000, u.data()) == 0);

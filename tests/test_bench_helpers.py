@@ -36,7 +36,7 @@ def test_flop_kinds_cover_the_object_kinds():
 
 
 def test_auto_tile_w_rule():
-    """The automatic tile shape (rtmi_device.hip auto_tile_w, mirrored by
+    """The automatic tile shape (csrc/rtmi_accel.h auto_tile_w, mirrored by
     rt.auto_tile_w for reporting): 8x8 unless 16x4 leaves fewer idle lanes."""
     import a_dive_into_ray_tracing_amd as rt
 
