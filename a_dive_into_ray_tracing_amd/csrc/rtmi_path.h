@@ -352,6 +352,18 @@ __device__ __forceinline__ int32_t hit_world(const SceneView<R> &sc, V3<R> o, V3
 // v_pk_fma_f32.  Each half is an IEEE fma, so results are bit-identical to
 // the scalar loop hit_world (and to the oracle).  Scenes are padded to a multiple of
 // 2*GP spheres with a dummy {0, 0, 0, 1e30} that can never be a candidate.
+// hit_big reads the same pairs and forms its four slots a group in plain
+// v_fma_f32 all the same (RTMI_BIG_PLAIN, default 1; 0 builds the packed
+// body): its group is short and runs once a segment in a kernel at its 64
+// VGPRs, where the nine ray terms duplicated into register pairs — 18
+// transient VGPRs and nine v_mov_b32 — cost more than the half-rate issue of
+// the FMAs: the register pairs, not the issue slots, are what the group
+// costs there (alone the two forms time alike, tools/valubench7.hip; in the
+// kernel the plain one is 1.2 % of the frame faster).  The same chains in
+// the same order, so the same bits (profiles/r14/big_plain/).
+#ifndef RTMI_BIG_PLAIN
+#define RTMI_BIG_PLAIN 1
+#endif
 typedef float f2v __attribute__((ext_vector_type(2)));
 struct SpherePair {
   f2v cx, cy, cz, S;
@@ -643,8 +655,9 @@ __device__ __forceinline__ void resolve_key(uint32_t key, float hb, float disc, 
 }
 
 // The big spheres (the ones kept out of the BVH / grid: the R = 1000 ground
-// and the r = 1 spheres) by the packed brute-force loop: group data and scene
-// indices through scalar loads, each half of a v_pk_fma_f32 an IEEE fma.
+// and the r = 1 spheres) brute force in groups of two pairs: group data and
+// scene indices through scalar loads, the slots' hb and disc by sphere_test's
+// chains in plain FMAs (RTMI_BIG_PLAIN, above SpherePair).
 // KEYS (the grid walk): best is a record-slot key, slot j's key rec_base + 16 j.
 template <int GP, bool KEYS = false, bool GMEM = false>
 __device__ __forceinline__ void hit_big(const Accel &acc_s, V3<float> d, float K, float a, float aL, float mx, float my,
@@ -654,11 +667,28 @@ __device__ __forceinline__ void hit_big(const Accel &acc_s, V3<float> d, float K
 #endif
                                         ) {
   static_assert(GP == 2, "the big-sphere loop resolves groups of two pairs");
+  typedef const __attribute__((address_space(4))) SpherePair *cpair_t;
+  const cpair_t cp = (cpair_t)(size_t)acc_s.big;
+#if RTMI_BIG_PLAIN
+  // sphere_test's chains per slot, the sphere's values the scalar operands
+  auto slot_terms = [&](float cx, float cy, float cz, float S, float &hb, float &disc) {
+    hb = __builtin_fmaf(-cx, d.x, __builtin_fmaf(-cy, d.y, __builtin_fmaf(-cz, d.z, K)));
+    const float ac = __builtin_fmaf(mx, cx, __builtin_fmaf(my, cy, __builtin_fmaf(mz, cz, __builtin_fmaf(a, S, aL))));
+    disc = __builtin_fmaf(hb, hb, -ac);
+  };
+  auto pair = [&](int q, f2v &hb, f2v &disc) {
+    const f2v cx = cp[q].cx, cy = cp[q].cy, cz = cp[q].cz, S = cp[q].S;
+    float h0, e0, h1, e1;
+    slot_terms(cx.x, cy.x, cz.x, S.x, h0, e0);
+    slot_terms(cx.y, cy.y, cz.y, S.y, h1, e1);
+    hb = f2v{h0, h1};
+    disc = f2v{e0, e1};
+  };
+#else
+  // the packed body: each half of a v_pk_fma_f32 the same IEEE fma
   const f2v DX = {d.x, d.x}, DY = {d.y, d.y}, DZ = {d.z, d.z}, KK = {K, K};
   const f2v MX = {mx, mx}, MY = {my, my}, MZ = {mz, mz};
   const f2v AA = {a, a}, AL = {aL, aL};
-  typedef const __attribute__((address_space(4))) SpherePair *cpair_t;
-  const cpair_t cp = (cpair_t)(size_t)acc_s.big;
   auto pair = [&](int q, f2v &hb, f2v &disc) {
     const f2v cx = cp[q].cx, cy = cp[q].cy, cz = cp[q].cz, S = cp[q].S;
     const f2v hz = __builtin_elementwise_fma(-cz, DZ, KK);
@@ -667,6 +697,7 @@ __device__ __forceinline__ void hit_big(const Accel &acc_s, V3<float> d, float K
                    __builtin_elementwise_fma(MZ, cz, __builtin_elementwise_fma(AA, S, AL))));
     disc = __builtin_elementwise_fma(hb, hb, -ac);
   };
+#endif
   // candidate iff disc >= +0 (sign clear; the dummies never are)
   auto cand = [](float x, int bit) { return (__float_as_int(x) >= 0 ? 1u : 0u) << bit; };
   for (int32_t q = 0; q < acc_s.nbig_pairs; q += 2) {
